@@ -13,7 +13,12 @@ inputs and launch plans => bit-identical results). Prints ONE JSON line on rank 
 invocation); the benchmark configuration's own dominant kernel is in `roofline_256`, marked `infinity_cache_assisted` (its three 67 MB
 operands fit the 256 MiB Infinity Cache). Fractions count the bytes a kernel MOVES by construction (BASELINE.md "Byte model").
 
+A plain run times the steps and prints the headline; everything else the line can carry (per-kernel profile and `roofline_256`, the
+512^3 `roofline` block, `cpu_baseline` + `parity`, `phi_level`) is measured only with `--full`. `--dump-outputs DIR` writes the fields
+the last timed step computed as DIR/<name>.npy, so that two builds can be compared output for output.
+
     python bench.py --gpus 1 --steps 10 --warmup 2
+    python bench.py --gpus 1 --steps 10 --warmup 2 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29500 bench.py --gpus 8
 """
 import argparse
@@ -238,6 +243,30 @@ def emit_record(record: dict):
         os.write(_RECORD_FD, line)
 
 
+DUMP_BYTES_MAX = 60 * 2 ** 20      # all .npy files of one --dump-outputs together stay below 64 MB
+
+
+def dump_outputs(directory, arrays, seed=0):
+    """ `--dump-outputs DIR`: the fields the timed path computed in its last step, one DIR/<name>.npy each (float32 / float64 as computed;
+    anything else as float64). An array larger than its share of DUMP_BYTES_MAX is written as a fixed sample of its flattened elements:
+    positions drawn by a generator seeded with `seed` from the element count alone, sorted -- the same positions in every run. """
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_BYTES_MAX // max(1, len(arrays))
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.dtype not in (torch.float32, torch.float64):
+            t = t.to(torch.float64)
+        flat = t.reshape(-1)
+        keep = share // flat.element_size()
+        if flat.numel() > keep:
+            idx = np.sort(np.random.default_rng(seed).choice(flat.numel(), size=keep, replace=False))
+            flat = flat.index_select(0, torch.from_numpy(idx).to(flat.device))
+            out = flat.cpu().numpy()
+        else:
+            out = t.cpu().numpy()
+        np.save(os.path.join(directory, f"{name}.npy"), out)
+
+
 def bench_config4(args, ctx, device, rank, world, dist, barrier, allreduce):
     """ strong scaling of the batched smoke workload: the SAME 8 simulations on 1 / 2 / 4 / 8 GPUs """
     total, n = args.batch_total, args.size if args.size != 256 else 512
@@ -254,6 +283,9 @@ def bench_config4(args, ctx, device, rank, world, dist, barrier, allreduce):
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0 and sim.batch > 0:          # (rank 0's own entries)
+        dump_outputs(args.dump_outputs, {"pressure": sim.p[:sim.batch], "smoke": sim.smoke[:sim.batch], "velocity_x": sim.v[0][:sim.batch],
+                                         "velocity_y": sim.v[1][:sim.batch], "relative_residual": rel})
     # ---- self-validation on EVERY rank (the first multi-GPU run of this workload will be the driver's): one reporting step on the owned
     # entries, then batch entry 0 recomputed alone on this rank with the analytic launch plans -- its bits must agree across ranks ----
     its_local, ok_local = [], True
@@ -322,6 +354,9 @@ def bench_smoke3d(args, ctx, lib, device, rank, world, dist, barrier, allreduce)
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"pressure": sim.p, "smoke": sim.smoke, "velocity_x": sim.v[0], "velocity_y": sim.v[1], "velocity_z": sim.v[2],
+                                         "relative_residual": rel})
     if rank == 0:
         # one more step with an event pair around every operation (C call) + the library's per-launch events for the projection's parts
         evs = []
@@ -403,6 +438,8 @@ def bench_slab(args, lib, device, rank, world, dist, barrier):
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:          # (rank 0's slab)
+        dump_outputs(args.dump_outputs, {"pressure": p, "velocity_x": vel[0], "velocity_y": vel[1], "velocity_z": vel[2]})
     its = torch.tensor([infos[0].iterations, int(infos[0].diverged)], device=device, dtype=torch.int64)
     every = [its.clone() for _ in range(world)]
     if dist is not None:
@@ -840,8 +877,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--size", type=int, default=256, help="cells per axis (BASELINE: 256)")
     ap.add_argument("--cg-iters", type=int, default=100)
-    ap.add_argument("--cpu-size", type=int, default=256, help="grid size of the CPU baseline sample and of the parity block (0 = skip); 256 = the metric's own configuration, ~30 s of NumPy")
-    ap.add_argument("--profile-steps", type=int, default=1, help="extra steps with per-launch hipEvent timing for the roofline")
+    ap.add_argument("--cpu-size", type=int, default=256, help="--full: grid size of the CPU baseline sample and of the parity block (0 = skip); 256 = the metric's own configuration, ~30 s of NumPy")
+    ap.add_argument("--profile-steps", type=int, default=1, help="--full: extra steps with per-launch hipEvent timing for the roofline")
     ap.add_argument("--workload", default="config2", choices=["config2", "config4", "slab", "smoke256"],
                     help="config2 (default, the BASELINE metric): 256^3 Taylor-Green replicas, weak scaling. config4: 8 x 512^2 batched smoke, the batch "
                          "sharded over the GPUs, strong scaling. slab: ONE --size^3 simulation decomposed into x-slabs over the GPUs (SURVEY §8 f4). smoke256: a 3-D smoke "
@@ -851,11 +888,16 @@ def main():
     ap.add_argument("--resident-cg", type=int, default=-1, choices=[-1, 0, 1, 2], help="-1: the library's default (r6: mode 1); resident solver for 2-D fp32 projections (phihip_set_resident_cg; config4: "
                     "the projection's CG iterations become ONE launch): 0 off, 1 up to the built-in cell limit, 2 whenever applicable")
     ap.add_argument("--batch-total", type=int, default=8, help="config4: simulations in the batch (all ranks together)")
-    ap.add_argument("--config3-size", type=int, default=512, help="grid size of the BASELINE configs[2] block = the `roofline` kernel (pressure solve only; 0 = skip)")
-    ap.add_argument("--pmc", type=int, default=1, help="1: run the rocprofv3 FETCH_SIZE / WRITE_SIZE passes for roofline.traffic inside this invocation")
+    ap.add_argument("--config3-size", type=int, default=512, help="--full: grid size of the BASELINE configs[2] block = the `roofline` kernel (pressure solve only; 0 = skip)")
+    ap.add_argument("--pmc", type=int, default=1, help="--full: 1: run the rocprofv3 FETCH_SIZE / WRITE_SIZE passes for roofline.traffic inside this invocation")
     ap.add_argument("--tuning", type=str, default="", help="rows,threads_per_row,chunk override of the CG tile")
     ap.add_argument("--advect-halo", type=int, default=-1, help="phihip_set_advect_halo: -1 adaptive reach (default), 0 gather kernels, 1 / 2 fixed reach of the LDS-staged advection passes (A/B of the policy)")
-    ap.add_argument("--phi-level", type=int, default=1, help="1: time the same steps through phiflow_amd.flow next to the C-ABI loop (`phi_level`; rank 0, N = 1, ~3 s)")
+    ap.add_argument("--phi-level", type=int, default=1, help="--full: 1: time the same steps through phiflow_amd.flow next to the C-ABI loop (`phi_level`; rank 0, N = 1, ~3 s)")
+    ap.add_argument("--full", action="store_true", help="config2: after the timed steps also measure what the headline does not need -- the profiled steps "
+                    "(--profile-steps, `roofline_256`), the CPU baseline and parity (--cpu-size), `phi_level` (--phi-level), the 512^3 `roofline` block "
+                    "(--config3-size, --pmc); without it those options have no effect and the keys are null or absent")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write the fields the last timed step computed as DIR/<name>.npy (float32 / float64, "
+                    "at most 64 MB in all: a larger field as a fixed, seeded sample of its elements)")
     args = ap.parse_args()
 
     # stdout carries exactly ONE line, the JSON record: libraries that write to file descriptor 1 behind Python's back (RCCL prints a
@@ -919,6 +961,9 @@ def main():
         elapsed = float(t.item())
     cells = n ** 3 * B
     value = cells * world * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"pressure": sim.p, "velocity_x": sim.v[0], "velocity_y": sim.v[1], "velocity_z": sim.v[2],
+                                         "relative_residual": sim.rel})
 
     # ---- the timed steps must have run the iterations they claim (an entry that freezes -- diverged / residual 0 -- makes the remaining
     # launches return at once and would overstate the throughput): one more step that reports, ON EVERY RANK; with it the bit checksum of
@@ -940,7 +985,7 @@ def main():
     # ---- benchmark configuration (256^3): hipEvent pairs around every launch on the solve stream, extra profiled steps ----
     extra = {}
     roofline_bench = None
-    if rank == 0 and args.profile_steps > 0:
+    if args.full and rank == 0 and args.profile_steps > 0:
         ctx.profile_enable(True)
         ctx.profile_read(reset=True)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -972,18 +1017,18 @@ def main():
         extra["plan"] = {name: ctx.query_plan(sim.grid, False, fam) for name, fam in (("matvec", 1), ("update_x2", 2), ("update_r", 3))}
 
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_size > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_size > 0:
         cpu, ref = cpu_baseline(args.cpu_size, args.cg_iters)
         extra["parity"] = parity_block(ctx, args.cpu_size, args.cg_iters, device, ref)
         del ref
         extra["cpu_cg_variants"] = cpu_cg_variants(96, 20)
 
-    if rank == 0 and world == 1 and args.phi_level and n == 256:
+    if args.full and rank == 0 and world == 1 and args.phi_level and n == 256:
         extra["phi_level"] = phi_level_block(ctx, lib, device, args.cg_iters)
 
     # ---- the HBM-resident configuration: 512^3 pressure solve (BASELINE configs[2]) -> `roofline` ----
     roofline = None
-    if rank == 0 and args.config3_size > 0:
+    if args.full and rank == 0 and args.config3_size > 0:
         del sim
         torch.cuda.empty_cache()
         if pinned_plans is not None:

@@ -7,7 +7,8 @@ import pytest
 from phiflow_amd import field_io
 from phiflow_amd.flow import BOUNDARY, PERIODIC, ZERO, Box, CenteredGrid, StaggeredGrid, combine_sides
 
-REF_FIXTURES = "/root/reference/tests/commit/field"
+# the two legacy files of the reference's tests/commit/field, stored unchanged as data fixtures
+REF_FIXTURES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "field")
 
 
 @pytest.mark.parametrize("ext", [ZERO, BOUNDARY, PERIODIC, combine_sides(x=BOUNDARY, y=(ZERO, BOUNDARY))])
@@ -28,7 +29,6 @@ def test_roundtrip(emu_backend, tmp_path, ext):
     np.testing.assert_array_equal(s.numpy(), s2.numpy())
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF_FIXTURES, "velo_001000.npz")), reason="reference fixtures not present")
 def test_read_reference_fixtures(emu_backend):
     """ tests/commit/field/test__scene.py:158-165 (legacy centred + staggered grids written by PhiFlow itself) """
     density = field_io.read(os.path.join(REF_FIXTURES, "dens_001000.npz"), emu_backend)

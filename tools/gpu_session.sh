@@ -35,7 +35,7 @@ stage_smoke() {
   timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "smoke rc=$?"; tail -1 $O/smoke.log
 }
 stage_bench() {             # the driver's own line
-  timeout 900 python bench.py --steps 20 --warmup 5 > $O/bench_n1.json 2> $O/bench_n1.err; echo "bench rc=$?"; head -c 400 $O/bench_n1.json; echo
+  timeout 900 python bench.py --steps 20 --warmup 5 --full > $O/bench_n1.json 2> $O/bench_n1.err; echo "bench rc=$?"; head -c 400 $O/bench_n1.json; echo
   py - <<PY
 import json
 try:
@@ -47,7 +47,7 @@ except Exception as e:
 PY
 }
 stage_bench_quick() {       # the 256^3 line without the side measurements
-  timeout 600 python bench.py --steps 20 --warmup 5 --pmc 0 --cpu-size 0 --phi-level 0 > $O/bench_quick.json 2> $O/bench_quick.err; echo "bench_quick rc=$?"
+  timeout 600 python bench.py --steps 20 --warmup 5 --full --pmc 0 --cpu-size 0 --phi-level 0 > $O/bench_quick.json 2> $O/bench_quick.err; echo "bench_quick rc=$?"
   py -c "import json;d=json.loads(open('$O/bench_quick.json').read().strip().splitlines()[-1]);print('ms_per_step', d['ms_per_step'], 'config3', d.get('config3',{}).get('ms_per_iteration'))"
 }
 stage_jit_debug() {         # the replay-after-_foreach_ record
