@@ -287,6 +287,20 @@ int phihip_diffuse_explicit_backward(phihip_ctx* ctx, const phihip_grid* grid, c
  * ACCUMULATED input gradient and `s` the output gradient */
 int phihip_diffuse_explicit_centered(phihip_ctx* ctx, const phihip_grid* grid, const void* s, const int32_t s_bc[3][2],
                                      const double s_val[3][2], void* out, double diffusivity_dt, int adjoint, void* stream);
+/* diffuse.explicit / diffuse.implicit of a CenteredGrid with a spatially varying and / or per-axis diffusivity (phi/physics/diffuse.py:13-60,
+ * :98-141; Heat_Flow.ipynb): the conservative flux form  u + sum_d (F_{i+1/2} - F_{i-1/2}),  F = min(kdt_d a_L, kdt_d a_R) / dx_d^2 (u_R - u_L),
+ * on all n + 1 faces per axis; ghost cells of u from s_bc / s_val, of the coefficient from c_bc / c_val (on an axis where u is periodic the two
+ * end faces are one face between the last and the first cell). coef: [c_batch][cells] with c_batch 1 (shared) or grid.batch, or NULL = 1
+ * everywhere (the per-axis weighted Laplacian). kdt[d] = k_d * dt' per axis d of the grid (signed: the minimum of the signed amounts).
+ * explicit: one substep, out = u + L u; adjoint != 0: `out` is the ACCUMULATED input gradient and `s` the output gradient.
+ * implicit: out = sharpen^-1(s) with sharpen(x) = x + L_{-kdt} x, CG from x0 = s (kdt[d] >= 0); solve / info like phihip_diffuse_implicit_centered. */
+int phihip_diffuse_explicit_centered_coef(phihip_ctx* ctx, const phihip_grid* grid, const void* s, const int32_t s_bc[3][2],
+                                          const double s_val[3][2], const void* coef, int c_batch, const int32_t c_bc[3][2],
+                                          const double c_val[3][2], const double kdt[3], void* out, int adjoint, void* stream);
+int phihip_diffuse_implicit_centered_coef(phihip_ctx* ctx, const phihip_grid* grid, const void* s, const int32_t s_bc[3][2],
+                                          const double s_val[3][2], const void* coef, int c_batch, const int32_t c_bc[3][2],
+                                          const double c_val[3][2], const double kdt[3], void* out, const phihip_solve* solve,
+                                          phihip_solve_info* info, void* stream);
 int phihip_centered_to_staggered_backward(phihip_ctx* ctx, const phihip_grid* grid, const int32_t s_bc[3][2],
                                           const double vector[3], const void* const grad_out[3], void* grad_s, void* stream);
 /* adjoint of phihip_make_incompressible (implicit-function gradient of the linear solve like phiml's solve_linear backward):

@@ -31,6 +31,7 @@ EXPORTED_SYMBOLS = (
     "phihip_diffuse_explicit_backward", "phihip_diffuse_explicit_centered", "phihip_diffuse_implicit", "phihip_diffuse_implicit_centered", "phihip_cg_solve_shifted",
     "phihip_slab_residual", "phihip_slab_matvec", "phihip_slab_update", "phihip_slab_state", "phihip_set_small_grid_solver",
     "phihip_grid_sample", "phihip_grid_sample_backward", "phihip_set_deferred_x_update", "phihip_set_advect_halo", "phihip_advect_fallback_stats", "phihip_set_advect_chunk", "phihip_set_advect_windows_2d", "phihip_query_advect_chunk", "phihip_set_autotune", "phihip_allreduce_residual", "phihip_set_single_reduction_cg", "phihip_set_resident_cg", "phihip_set_advect_dma", "phihip_workspace_placement",
+    "phihip_diffuse_explicit_centered_coef", "phihip_diffuse_implicit_centered_coef",
 )
 
 
@@ -214,6 +215,12 @@ class Library:
         d.phihip_diffuse_implicit.argtypes = [c_void_p, POINTER(Grid), POINTER(_Ptr3), POINTER(_Ptr3), c_double, POINTER(Solve), POINTER(SolveInfo), c_void_p]
         d.phihip_diffuse_implicit_centered.argtypes = [c_void_p, POINTER(Grid), c_void_p, POINTER((c_int32 * 2) * 3), POINTER((c_double * 2) * 3), c_void_p,
                                                        c_double, POINTER(Solve), POINTER(SolveInfo), c_void_p]
+        d.phihip_diffuse_explicit_centered_coef.argtypes = [c_void_p, POINTER(Grid), c_void_p, POINTER((c_int32 * 2) * 3), POINTER((c_double * 2) * 3),
+                                                            c_void_p, c_int, POINTER((c_int32 * 2) * 3), POINTER((c_double * 2) * 3),
+                                                            POINTER(c_double * 3), c_void_p, c_int, c_void_p]
+        d.phihip_diffuse_implicit_centered_coef.argtypes = [c_void_p, POINTER(Grid), c_void_p, POINTER((c_int32 * 2) * 3), POINTER((c_double * 2) * 3),
+                                                            c_void_p, c_int, POINTER((c_int32 * 2) * 3), POINTER((c_double * 2) * 3),
+                                                            POINTER(c_double * 3), c_void_p, POINTER(Solve), POINTER(SolveInfo), c_void_p]
         d.phihip_profile_enable.argtypes = [c_void_p, c_int]
         d.phihip_profile_read.argtypes = [c_void_p, POINTER(c_int32 * K_COUNT), POINTER(c_double * K_COUNT), c_int]
         d.phihip_set_tuning.argtypes = [c_void_p, c_int, c_int, c_int]
@@ -482,6 +489,27 @@ class Context:
         info = (SolveInfo * grid.batch)() if want_info else None
         self.lib.check(self.lib.dll.phihip_diffuse_implicit_centered(self.handle, ctypes.byref(grid), s, ctypes.byref(bc), ctypes.byref(val), out,
                                                                      float(diffusivity_dt), ctypes.byref(solve), info, stream or None))
+        return list(info) if want_info else None
+
+    def diffuse_explicit_centered_coef(self, grid, s, s_bc, s_val, coef, c_batch, c_bc, c_val, kdt, out, adjoint=False, stream=0):
+        """ one substep of diffuse.explicit with a varying / per-axis diffusivity: out = s + L s (adjoint: out += (I + L)^T s);
+        coef = 0 -> 1 everywhere; kdt = k_d * dt' per grid axis """
+        bc, val = self._scalar_bc(grid, s_bc, s_val)
+        cbc, cval = self._scalar_bc(grid, c_bc if coef else s_bc, c_val if coef else s_val)
+        k = (c_double * 3)(*[float(x) for x in kdt], *([0.0] * (3 - len(kdt))))
+        self.lib.check(self.lib.dll.phihip_diffuse_explicit_centered_coef(self.handle, ctypes.byref(grid), s, ctypes.byref(bc), ctypes.byref(val), coef or None,
+                                                                          int(c_batch), ctypes.byref(cbc), ctypes.byref(cval), ctypes.byref(k), out,
+                                                                          int(bool(adjoint)), stream or None))
+
+    def diffuse_implicit_centered_coef(self, grid, s, s_bc, s_val, coef, c_batch, c_bc, c_val, kdt, out, solve: Solve, stream=0, want_info=True):
+        """ diffuse.implicit with a varying / per-axis diffusivity; returns [batch] SolveInfo (None with want_info=False: no host read-back) """
+        bc, val = self._scalar_bc(grid, s_bc, s_val)
+        cbc, cval = self._scalar_bc(grid, c_bc if coef else s_bc, c_val if coef else s_val)
+        k = (c_double * 3)(*[float(x) for x in kdt], *([0.0] * (3 - len(kdt))))
+        info = (SolveInfo * grid.batch)() if want_info else None
+        self.lib.check(self.lib.dll.phihip_diffuse_implicit_centered_coef(self.handle, ctypes.byref(grid), s, ctypes.byref(bc), ctypes.byref(val), coef or None,
+                                                                          int(c_batch), ctypes.byref(cbc), ctypes.byref(cval), ctypes.byref(k), out,
+                                                                          ctypes.byref(solve), info, stream or None))
         return list(info) if want_info else None
 
     def profile_enable(self, enable: bool):

@@ -233,6 +233,58 @@ class DiffuseCentered(torch.autograd.Function):
         return None, gin
 
 
+class DiffuseCoefCentered(torch.autograd.Function):
+    """ one substep of diffuse.explicit with a coefficient field / per-axis factors (csrc/diffuse_coef.hpp). The linear part of the operator is
+    symmetric, so the vector-Jacobian product is the same stencil with homogeneous walls (adjoint flag: accumulated into gin). """
+
+    @staticmethod
+    def forward(ctx, meta, s):
+        s = s.contiguous()
+        out = torch.empty_like(s)
+        be, c = meta['be'], meta['coef']
+        be.ctx.diffuse_explicit_centered_coef(meta['grid'], s.data_ptr(), meta['s_codes'], meta['s_val'], c.data_ptr() if c is not None else 0,
+                                              meta['c_batch'], meta['c_codes'], meta['c_val'], meta['kdt'], out.data_ptr(), False, be.stream())
+        ctx.meta = meta
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        meta = ctx.meta
+        be, c = meta['be'], meta['coef']
+        g = grad.contiguous()
+        gin = torch.zeros_like(g)
+        be.ctx.diffuse_explicit_centered_coef(meta['grid'], g.data_ptr(), meta['s_codes'], meta['s_val'], c.data_ptr() if c is not None else 0,
+                                              meta['c_batch'], meta['c_codes'], meta['c_val'], meta['kdt'], gin.data_ptr(), True, be.stream())
+        return None, gin
+
+
+class DiffuseImplicitCoefCentered(torch.autograd.Function):
+    """ diffuse.implicit with a coefficient field / per-axis factors: out = sharpen^-1(s). Symmetric operator: the vector-Jacobian product is
+    one more solve with the upstream gradient as right-hand side and homogeneous walls (`solve.gradient_solve` if given). """
+
+    @staticmethod
+    def forward(ctx, meta, s):
+        s = s.contiguous()
+        out = torch.empty_like(s)
+        be, c = meta['be'], meta['coef']
+        meta['infos'] = be.ctx.diffuse_implicit_centered_coef(meta['grid'], s.data_ptr(), meta['s_codes'], meta['s_val'], c.data_ptr() if c is not None else 0,
+                                                              meta['c_batch'], meta['c_codes'], meta['c_val'], meta['kdt'], out.data_ptr(), meta['csolve'],
+                                                              be.stream())
+        ctx.meta = meta
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        meta = ctx.meta
+        be, c = meta['be'], meta['coef']
+        g = grad.contiguous()
+        gin = torch.empty_like(g)
+        zero = [[0.0, 0.0] for _ in meta['s_val']]
+        be.ctx.diffuse_implicit_centered_coef(meta['grid'], g.data_ptr(), meta['s_codes'], zero, c.data_ptr() if c is not None else 0, meta['c_batch'],
+                                              meta['c_codes'], meta['c_val'], meta['kdt'], gin.data_ptr(), meta['csolve_bwd'], be.stream())
+        return None, gin
+
+
 class CenteredToStaggered(torch.autograd.Function):
     """ resample(s * vector, to=velocity) """
 

@@ -355,7 +355,8 @@ int phihip_ctx_create(int device, phihip_ctx** out) {
 int phihip_ctx_destroy(phihip_ctx* ctx) {
     if (!ctx) return PHIHIP_OK;
     (void)hipSetDevice(ctx->device);
-    DeviceBuffer* bufs[] = {&ctx->ws_r, &ctx->ws_d0, &ctx->ws_d1, &ctx->ws_div, &ctx->ws_part, &ctx->ws_state, &ctx->ws_scalars, &ctx->ws_rhs, &ctx->ws_adv, &ctx->ws_adv_flags, &ctx->ws_adj_q, &ctx->ws_adj_l, &ctx->ws_cg1, &ctx->ws_adj_g, &ctx->ws_res, &ctx->ws_adv_const};
+    DeviceBuffer* bufs[] = {&ctx->ws_r, &ctx->ws_d0, &ctx->ws_d1, &ctx->ws_div, &ctx->ws_part, &ctx->ws_state, &ctx->ws_scalars, &ctx->ws_rhs, &ctx->ws_adv, &ctx->ws_adv_flags, &ctx->ws_adj_q, &ctx->ws_adj_l, &ctx->ws_cg1, &ctx->ws_adj_g, &ctx->ws_res, &ctx->ws_adv_const,
+                            &ctx->ws_coef_r, &ctx->ws_coef_d0, &ctx->ws_coef_d1, &ctx->ws_coef_part, &ctx->ws_coef_state, &ctx->ws_coef_rhs};
     for (DeviceBuffer* b : bufs)
         if (b->ptr) (void)hipFree(b->ptr);
     if (ctx->host_state) (void)hipHostFree(ctx->host_state);
@@ -377,7 +378,8 @@ int phihip_ctx_destroy(phihip_ctx* ctx) {
 int phihip_workspace_bytes(const phihip_ctx* ctx, size_t* bytes) {
     PHIHIP_REQUIRE(ctx && bytes, "ctx / bytes is NULL");
     *bytes = ctx->ws_r.bytes + ctx->ws_d0.bytes + ctx->ws_d1.bytes + ctx->ws_div.bytes + ctx->ws_part.bytes + ctx->ws_state.bytes +
-             ctx->ws_scalars.bytes + ctx->ws_rhs.bytes + ctx->ws_adv.bytes + ctx->ws_adv_flags.bytes + ctx->ws_adj_q.bytes + ctx->ws_adj_l.bytes + ctx->ws_cg1.bytes + ctx->ws_adj_g.bytes + ctx->ws_res.bytes;
+             ctx->ws_scalars.bytes + ctx->ws_rhs.bytes + ctx->ws_adv.bytes + ctx->ws_adv_flags.bytes + ctx->ws_adj_q.bytes + ctx->ws_adj_l.bytes + ctx->ws_cg1.bytes + ctx->ws_adj_g.bytes + ctx->ws_res.bytes +
+             ctx->ws_coef_r.bytes + ctx->ws_coef_d0.bytes + ctx->ws_coef_d1.bytes + ctx->ws_coef_part.bytes + ctx->ws_coef_state.bytes + ctx->ws_coef_rhs.bytes;
     return PHIHIP_OK;
 }
 
@@ -986,6 +988,52 @@ int phihip_diffuse_implicit_centered(phihip_ctx* ctx, const phihip_grid* grid, c
     PHIHIP_TRY(check_solve(solve));
     note_align(v, sfield); note_align(v, out);
     return run_diffuse_implicit_centered(ctx, v, sfield, s_bc, s_val, out, diffusivity_dt, solve, info, s);
+}
+
+// the coefficient of the *_coef entry points: batch 1 or grid.batch, its own extrapolation (periodicity need not match u's)
+static int check_coef(const GridView& v, const void* coef, int c_batch, const int32_t c_bc[3][2], const double kdt[3], const char* what) {
+    PHIHIP_REQUIRE(kdt != nullptr, "%s: kdt is NULL", what);
+    for (int d = 0; d < v.rank; ++d) PHIHIP_REQUIRE(kdt[d] == kdt[d], "%s: kdt[%d] is NaN", what, d);
+    if (!coef) return PHIHIP_OK;
+    PHIHIP_REQUIRE(c_batch == 1 || c_batch == v.batch, "%s: c_batch must be 1 or grid.batch (%d), got %d", what, v.batch, c_batch);
+    PHIHIP_REQUIRE(c_bc != nullptr, "%s: c_bc is NULL", what);
+    for (int d = 0; d < v.rank; ++d)
+        for (int side = 0; side < 2; ++side)
+            PHIHIP_REQUIRE(c_bc[d][side] >= PHIHIP_BC_PERIODIC && c_bc[d][side] <= PHIHIP_BC_OPEN, "%s: c_bc[%d][%d] invalid", what, d, side);
+    return PHIHIP_OK;
+}
+
+// kdt per grid axis -> per internal axis
+static void internal_kdt(const GridView& v, const double kdt[3], double out[3]) {
+    for (int a = 0; a < 3; ++a) out[a] = a < v.ax0 ? 0.0 : kdt[a - v.ax0];
+}
+
+int phihip_diffuse_explicit_centered_coef(phihip_ctx* ctx, const phihip_grid* grid, const void* sfield, const int32_t s_bc[3][2],
+                                          const double s_val[3][2], const void* coef, int c_batch, const int32_t c_bc[3][2],
+                                          const double c_val[3][2], const double kdt[3], void* out, int adjoint, void* stream) {
+    PHIHIP_ENTER(ctx, grid);
+    PHIHIP_REQUIRE(sfield && out && s_bc && sfield != out && coef != out, "diffuse_explicit_centered_coef: NULL or aliased argument");
+    PHIHIP_TRY(check_scalar_bc(v, s_bc, "diffuse_explicit_centered_coef"));
+    PHIHIP_TRY(check_coef(v, coef, c_batch, c_bc, kdt, "diffuse_explicit_centered_coef"));
+    double k[3];
+    internal_kdt(v, kdt, k);
+    return run_diffuse_coef_explicit(ctx, v, sfield, s_bc, s_val, coef, c_batch, coef ? c_bc : s_bc, c_val, k, adjoint, out, s);
+}
+
+int phihip_diffuse_implicit_centered_coef(phihip_ctx* ctx, const phihip_grid* grid, const void* sfield, const int32_t s_bc[3][2],
+                                          const double s_val[3][2], const void* coef, int c_batch, const int32_t c_bc[3][2],
+                                          const double c_val[3][2], const double kdt[3], void* out, const phihip_solve* solve,
+                                          phihip_solve_info* info, void* stream) {
+    PHIHIP_ENTER(ctx, grid);
+    PHIHIP_REQUIRE(sfield && out && s_bc && sfield != out && coef != out, "diffuse_implicit_centered_coef: NULL or aliased argument");
+    PHIHIP_TRY(check_scalar_bc(v, s_bc, "diffuse_implicit_centered_coef"));
+    PHIHIP_TRY(check_coef(v, coef, c_batch, c_bc, kdt, "diffuse_implicit_centered_coef"));
+    for (int d = 0; d < v.rank; ++d)
+        PHIHIP_REQUIRE(kdt[d] >= 0.0, "diffuse_implicit_centered_coef: kdt[%d] must be >= 0 (the operator is not positive definite otherwise)", d);
+    PHIHIP_TRY(check_solve(solve));
+    double k[3];
+    internal_kdt(v, kdt, k);
+    return run_diffuse_coef_implicit(ctx, v, sfield, s_bc, s_val, coef, c_batch, coef ? c_bc : s_bc, c_val, k, solve, info, out, s);
 }
 
 int phihip_query_plan(phihip_ctx* ctx, const phihip_grid* grid, int has_flags, int family, int32_t out[6]) {

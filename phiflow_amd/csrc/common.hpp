@@ -140,6 +140,8 @@ struct phihip_ctx {
     phihip::Tuning tuning[5];   // per kernel family: 0 = APPLY / RESID, 1 = MATVEC, 2 = UPDATE, 3 = UPDATE_R, 4 = CG1 (fused iteration)
     // workspace (grown on demand, reused between calls)
     phihip::DeviceBuffer ws_r, ws_d0, ws_d1, ws_div, ws_part, ws_state, ws_scalars, ws_rhs, ws_adv, ws_adv_flags, ws_adj_q, ws_adj_l, ws_cg1, ws_adj_g, ws_res, ws_adv_const;
+    // diffusion with a varying / per-axis diffusivity (diffuse_coef.hpp): its own CG vectors, partial sums, control blocks and right-hand side
+    phihip::DeviceBuffer ws_coef_r, ws_coef_d0, ws_coef_d1, ws_coef_part, ws_coef_state, ws_coef_rhs;
     int adv_last_nblk = 0;        // (tile, plane) units of the most recent LDS-staged advection launch (capacity of its fix-up work list)
     bool adv_ctl_clear = false;   // the work list's control block in ws_adv_flags has been zeroed
     // Adaptive reach (r4). Each LDS-staged pass publishes how many (tile, plane) units fell back to the gather path (the fix-up launch writes
@@ -365,6 +367,12 @@ int run_diffuse(phihip_ctx*, const GridView&, const void* const v[3], void* cons
 int run_diffuse_implicit(phihip_ctx*, const GridView&, const void* const v[3], void* const out[3], double kdt, const phihip_solve*, phihip_solve_info*, hipStream_t);
 int run_diffuse_implicit_centered(phihip_ctx*, const GridView&, const void* s, const int32_t s_bc[3][2], const double s_val[3][2], void* out, double kdt,
                                   const phihip_solve*, phihip_solve_info*, hipStream_t);
+// diffusion with a varying / per-axis diffusivity (diffuse_coef.hpp): coef = NULL means 1 everywhere; kdt per INTERNAL axis
+int run_diffuse_coef_explicit(phihip_ctx*, const GridView&, const void* u, const int32_t s_bc[3][2], const double s_val[3][2], const void* coef, int c_batch,
+                              const int32_t c_bc[3][2], const double c_val[3][2], const double kdt[3], int adjoint, void* out, hipStream_t);
+int run_diffuse_coef_implicit(phihip_ctx*, const GridView&, const void* u, const int32_t s_bc[3][2], const double s_val[3][2], const void* coef, int c_batch,
+                              const int32_t c_bc[3][2], const double c_val[3][2], const double kdt[3], const phihip_solve* solve, phihip_solve_info* info,
+                              void* out, hipStream_t);
 int run_laplace_apply(phihip_ctx*, const GridView&, const uint8_t* flags, int mask_batch, const void* p, void* out, hipStream_t);
 int run_laplace_apply_multi(phihip_ctx*, const GridView* lattices, int count, const void* const* in, void* const* out, hipStream_t);   // MODE_APPLY, no flags: lattices of one tile configuration share a launch
 int run_export_residuals(phihip_ctx*, int batch, double* out, hipStream_t);

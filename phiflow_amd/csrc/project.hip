@@ -1,10 +1,12 @@
 // project.hip -- the non-iterative stencils of fluid.make_incompressible (/root/reference phi/physics/fluid.py:94-162):
 // divergence of the staggered velocity (+ active mask, + mean balance), pressure-gradient subtraction, obstacle flags,
-// soft obstacle scaling, and the explicit diffusion stencil (phi/physics/diffuse.py:13-60).
+// soft obstacle scaling, and the explicit diffusion stencil (phi/physics/diffuse.py:13-60); diffusion with a varying / per-axis
+// diffusivity lives in diffuse_coef.hpp.
 // All are single-pass HBM-bound kernels: one thread per output sample, fast axis on consecutive lanes.
 #include <stdlib.h>
 
 #include "common.hpp"
+#include "diffuse_coef.hpp"
 
 namespace phihip {
 

@@ -1,7 +1,10 @@
 """
 Explicit and implicit diffusion on the HIP backend (reference: phi/physics/diffuse.py:13-92).
+The diffusivity is a number, a per-axis vector (`vec(x=1, y=2)` or a tuple), a centred `Field` (Heat_Flow.ipynb's conductivity) or a
+lazy `field * (k_x, k_y)`; the last three run on the flux-form kernels of csrc/diffuse_coef.hpp.
 """
 import warnings
+from typing import List, Optional, Sequence
 
 import torch
 
@@ -10,14 +13,69 @@ from .extrapolation import ConstantExtrapolation, resolve
 from .field import Field, _ptrs
 
 
-def explicit(u: Field, diffusivity: float, dt: float, substeps: int = 1, order: int = 2) -> Field:
+def _scalar_walls(f: Field):
+    """ (codes, constants) of a centred field's extrapolation for the C ABI (s_bc / s_val) """
+    codes, vals = resolve(f.boundary, f.dims)
+    val = [[vals[a][s][0] if isinstance(f.boundary.side(d, bool(s)), ConstantExtrapolation) else 0.0 for s in range(2)] for a, d in enumerate(f.dims)]
+    return codes, val
+
+
+def _diffusivity(u: Field, diffusivity, what: str):
+    """ -> (None, k) for a number (the constant-coefficient path), else (coefficient Field on u's grid or None, per-axis factors [D]).
+    A Field that does not live on u's grid is resampled first (`amount.at(u)`, diffuse.py:55-56), keeping its own extrapolation. """
+    from .geom import Vector
+    if isinstance(diffusivity, Field):
+        if u.is_staggered:
+            raise NotImplementedError(f"{what}: a Field diffusivity needs a CenteredGrid: spatially varying diffusion is only defined for "
+                                      f"centred grids (phi/physics/diffuse.py:138)")
+        if diffusivity.is_staggered:
+            raise NotImplementedError(f"{what}: the diffusivity must be a CenteredGrid (a scalar per cell), got a StaggeredGrid")
+        if autodiff.needs_grad(diffusivity.values):
+            raise NotImplementedError(f"{what}: gradients with respect to the diffusivity are not implemented; detach it (stop_gradient)")
+        factors = list(diffusivity.vector_scale) if diffusivity.vector_scale is not None else [1.0] * u.spatial_rank
+        coef = Field(diffusivity.resolution, diffusivity.bounds, diffusivity.boundary, diffusivity.values, False, diffusivity.backend, diffusivity.batched)
+        if coef.dims != u.dims or coef.resolution != u.resolution or tuple(coef.bounds.lower) != tuple(u.bounds.lower) \
+                or tuple(coef.bounds.upper) != tuple(u.bounds.upper):
+            from . import sampling
+            coef = sampling.resample_general(coef, u)
+            coef = Field(coef.resolution, coef.bounds, diffusivity.boundary, coef.values, False, coef.backend, coef.batched)
+        if coef.batch_size not in (1, u.batch_size):
+            raise NotImplementedError(f"{what}: a diffusivity with batch {coef.batch_size} for a field with batch {u.batch_size} (batch-valued "
+                                      f"diffusivities are not implemented)")
+        return coef, factors
+    if isinstance(diffusivity, Vector):
+        missing = [d for d in u.dims if d not in diffusivity]
+        if missing:
+            raise ValueError(f"{what}: the diffusivity vector {dict(diffusivity)} has no component for {missing}")
+        factors = [float(diffusivity[d]) for d in u.dims]
+    elif isinstance(diffusivity, (tuple, list)):
+        if len(diffusivity) != u.spatial_rank:
+            raise ValueError(f"{what}: {len(diffusivity)} diffusivities for a {u.spatial_rank}-D field")
+        factors = [float(k) for k in diffusivity]
+    else:
+        return None, float(diffusivity)
+    if all(k == factors[0] for k in factors):
+        return None, factors[0]             # an isotropic vector is the number: same kernels, same bits
+    if u.is_staggered:
+        raise NotImplementedError(f"{what}: a per-axis diffusivity needs a CenteredGrid (the reference's laplace(weights=...) of a staggered "
+                                  f"field is not implemented here)")
+    return None, factors
+
+
+def explicit(u: Field, diffusivity, dt: float, substeps: int = 1, order: int = 2) -> Field:
     """ Simulate a finite-time diffusion process of the form dF/dt = α · ΔF with explicit Euler steps (`diffuse.explicit`,
     order 2) on a StaggeredGrid or a CenteredGrid. The field's own extrapolation pads the stencil (tangential wall values of a
-    velocity matter). Differentiable (adjoint stencil kernels). """
+    velocity matter). Differentiable w.r.t. u (adjoint stencil kernels). `diffusivity`: a number; for a CenteredGrid also a per-axis
+    `vec(...)` / tuple, a centred `Field` (resampled to u's grid if it lives elsewhere) or a lazy `Field * (k_x, k_y)` -- the conservative
+    flux form of diffuse.py:129-141. """
     from .field import require_plain
     require_plain(u, 'diffuse.explicit')
     if order != 2:
         raise NotImplementedError("HIP backend: diffuse.explicit implements order=2 only")
+    coef, k = _diffusivity(u, diffusivity, 'diffuse.explicit')
+    if coef is not None or isinstance(k, list):
+        return _explicit_coef(u, coef, k if isinstance(k, list) else [k] * u.spatial_rank, dt, substeps)
+    diffusivity = k
     amount = diffusivity * dt
     # CFL warning of the reference (diffuse.py:49-54)
     ratio = max(amount / substeps / (h * h) for h in u.dx)
@@ -57,14 +115,48 @@ def explicit(u: Field, diffusivity: float, dt: float, substeps: int = 1, order: 
     return u.with_values(cur)
 
 
-def implicit(field: Field, diffusivity: float, dt: float, solve=None, order: int = 2) -> Field:
+def _explicit_coef(u: Field, coef: Optional[Field], factors: List[float], dt: float, substeps: int) -> Field:
+    """ diffuse.explicit with a coefficient field and / or per-axis factors: `substeps` launches of the flux-form stencil (diffuse_coef.hpp) """
+    from . import _capi
+    from .field import _torch_dtype_code
+    from .jit import is_tracing
+    kdt = [k * dt / substeps for k in factors]
+    # CFL warning of the reference (diffuse.py:48-54): the maximum of the amount over space (a host read: skipped inside a jit_compile trace)
+    if not is_tracing():
+        amax = float(coef.values.max()) if coef is not None else 1.0
+        ratio = max(amax * k / (h * h) for k, h in zip(kdt, u.dx))
+        if ratio > 0.5:
+            warnings.warn(f"CFL condition violated in diffuse.explicit: max(diffusivity)*dt/dx^2 = {ratio:.3f} > 0.5, consider more substeps",
+                          RuntimeWarning)
+    be = u.backend
+    s_codes, s_val = _scalar_walls(u)
+    grid = _capi.make_grid(u.spatial_rank, _torch_dtype_code(u.dtype), u.batch_size, list(u.resolution.values()), u.bounds.lower, u.bounds.upper,
+                           [[0 if c == 0 else 2 for c in pair] for pair in s_codes])
+    c = coef.values.to(u.dtype).contiguous() if coef is not None else None
+    c_codes, c_val = _scalar_walls(coef) if coef is not None else (s_codes, s_val)
+    meta = dict(be=be, grid=grid, kdt=kdt, s_codes=s_codes, s_val=s_val, coef=c, c_batch=c.shape[0] if c is not None else 1, c_codes=c_codes, c_val=c_val)
+    cur = u.values.contiguous()
+    tracked = autodiff.needs_grad(cur)
+    for _ in range(substeps):
+        if tracked:
+            cur = autodiff.DiffuseCoefCentered.apply(meta, cur)
+        else:
+            out = torch.empty_like(cur)
+            be.ctx.diffuse_explicit_centered_coef(grid, cur.data_ptr(), s_codes, s_val, c.data_ptr() if c is not None else 0, meta['c_batch'], c_codes,
+                                                  c_val, kdt, out.data_ptr(), False, be.stream())
+            cur = out
+    return u.with_values(cur)
+
+
+def implicit(field: Field, diffusivity, dt: float, solve=None, order: int = 2) -> Field:
     """ Implicit Euler diffusion (`diffuse.implicit`, phi/physics/diffuse.py:63-92; Heat_Flow.ipynb, Burgers.ipynb): solves
     `(1 - diffusivity * dt * laplace) u = field` with CG from `x0 = field` -- `solve_linear(sharpen, y=field, solve)` with
     `sharpen(x) = explicit(x, diffusivity, -dt)`. The solver is the matrix-free CG of the pressure path (same kernels, operator
     I - k dt L) on the field's own lattice and extrapolation; every component of a StaggeredGrid is solved separately (the
     operator does not couple them). `solve`: `Solve('CG' | 'CG-adaptive', rel_tol, abs_tol, max_iterations)`; raises
     `NotConverged` / `Diverged` like `solve_linear` unless suppressed. Differentiable w.r.t. the field: the operator is symmetric, the
-    backward pass is one more solve (with `solve.gradient_solve` if given) of the same system with homogeneous boundary constants. """
+    backward pass is one more solve (with `solve.gradient_solve` if given) of the same system with homogeneous boundary constants.
+    `diffusivity` takes the forms of `explicit`; a Field or per-axis one runs the CG of csrc/diffuse_coef.hpp on sharpen = I + L_{-dt a}. """
     from .field import require_plain, _torch_dtype_code
     from .solve import Solve, SolveInfo
     from .jit import is_tracing
@@ -87,7 +179,28 @@ def implicit(field: Field, diffusivity: float, dt: float, solve=None, order: int
         if tracked:
             raise NotImplementedError("HIP backend: gradients through a jit_compile'd function are not implemented")
     csolve_bwd = (solve.gradient_solve or solve).to_c(fp64)
-    kdt = float(diffusivity) * float(dt)
+    coef, k = _diffusivity(field, diffusivity, 'diffuse.implicit')
+    if coef is not None or isinstance(k, list):
+        factors = k if isinstance(k, list) else [k] * field.spatial_rank
+        kdt = [f * float(dt) for f in factors]
+        s_codes, s_val = _scalar_walls(field)
+        grid = _capi.make_grid(field.spatial_rank, _torch_dtype_code(field.dtype), field.batch_size, list(field.resolution.values()), field.bounds.lower,
+                               field.bounds.upper, [[0 if c == 0 else 2 for c in pair] for pair in s_codes])
+        c = coef.values.to(field.dtype).contiguous() if coef is not None else None
+        c_codes, c_val = _scalar_walls(coef) if coef is not None else (s_codes, s_val)
+        meta = dict(be=be, grid=grid, kdt=kdt, s_codes=s_codes, s_val=s_val, coef=c, c_batch=c.shape[0] if c is not None else 1, c_codes=c_codes,
+                    c_val=c_val, csolve=csolve, csolve_bwd=csolve_bwd)
+        cur = field.values.contiguous()
+        if tracked:
+            out = autodiff.DiffuseImplicitCoefCentered.apply(meta, cur)
+            infos = meta['infos']
+        else:
+            out = torch.empty_like(cur)
+            infos = be.ctx.diffuse_implicit_centered_coef(grid, cur.data_ptr(), s_codes, s_val, c.data_ptr() if c is not None else 0, meta['c_batch'],
+                                                          c_codes, c_val, kdt, out.data_ptr(), csolve, be.stream(), want_info=not traced)
+        result = field.with_values(out)
+        return _finish_implicit(result, infos, solve)
+    kdt = float(k) * float(dt)
     if field.is_staggered:
         cur = [t.contiguous() for t in field.values]
         if tracked:
@@ -113,6 +226,13 @@ def implicit(field: Field, diffusivity: float, dt: float, solve=None, order: int
             out = torch.empty_like(cur)
             infos = be.ctx.diffuse_implicit_centered(grid, cur.data_ptr(), s_codes, s_val, out.data_ptr(), kdt, csolve, be.stream(), want_info=not traced)
         result = field.with_values(out)
+    return _finish_implicit(result, infos, solve)
+
+
+def _finish_implicit(result: Field, infos, solve) -> Field:
+    """ solve_linear semantics: NotConverged / Diverged unless suppressed; the SolveInfo rides on the result (no infos: traced, nothing read back) """
+    from .solve import SolveInfo
+    from .fluid import _raise_if_failed
     if infos is not None:
         info = SolveInfo(solve, [i.iterations for i in infos], [i.residual_sq for i in infos], [i.rhs_sq for i in infos],
                          [bool(i.converged) for i in infos], [bool(i.diverged) for i in infos])
