@@ -149,6 +149,26 @@ int phihip_centered_to_staggered(phihip_ctx* ctx, const phihip_grid* grid, const
                                  const double s_val[3][2], const double vector[3], int accumulate, void* const out[3],
                                  void* stream);
 
+/* ---- centred vector fields (CenteredGrid(Noise(vector='x,y')), v.at_centers(), Burgers' equation) -----------------------------------
+ * Layout: a centred field with C components is ONE dense array [batch][C][res...], component-major; component c of batch entry b is a
+ * contiguous centred scalar grid (a centred velocity has C = grid.rank, component d along grid axis d). Batches: an input of batch 1 is
+ * shared by all grid.batch entries; outputs have grid.batch. Outputs must not alias inputs. */
+/* semi-Lagrangian advection, euler back-trace, of a C-component centred field by a centred velocity [velocity_batch][rank][res...] on the
+ * same grid (phi/physics/advect.py:20-24,156-179): lookup = x - dt u(x), all C components gathered with the same taps. Pass the same
+ * pointer as field and velocity (C = rank) for self-advection. s_bc / s_val = the field's extrapolation, shared by its components
+ * (PERIODIC wrap / OPEN zero-gradient / CLOSED constant); grid.res / bounds give the cell size, grid.bc only its periodicity (a centred
+ * field with one cell between two constant sides is accepted). components in 1..16. */
+int phihip_advect_centered_vector(phihip_ctx* ctx, const phihip_grid* grid, const void* field, int field_batch, int components,
+                                  const int32_t s_bc[3][2], const double s_val[3][2], const void* velocity, int velocity_batch,
+                                  void* out, double dt, void* stream);
+/* staggered -> cell centres (`velocity.at_centers()`, phi/field/_resample.py:241-259,341-364): out [grid.batch][rank][res...],
+ * component d = mean of the cell's two d-faces; faces that are not stored take the wall constant, PERIODIC axes wrap. */
+int phihip_staggered_to_centered(phihip_ctx* ctx, const phihip_grid* grid, const void* const velocity[3], void* out, void* stream);
+/* centred vector -> the stored faces of the staggered grid `grid` (phi/field/_resample.py:148-153): out_d = mean of component d in the
+ * two cells adjacent to each stored d-face, outside cells from the field's extrapolation s_bc / s_val. field [field_batch][rank][res...]. */
+int phihip_centered_vector_to_staggered(phihip_ctx* ctx, const phihip_grid* grid, const void* field, int field_batch,
+                                        const int32_t s_bc[3][2], const double s_val[3][2], void* const out[3], void* stream);
+
 /* ---- a7: obstacle masks (phi/physics/fluid.py:130-137) ---------------------------------------------------------- */
 /* Packs per-cell stencil flags (1 byte / cell): bit 2*axis+side = the face on that side is open for flux
  * (hard_bcs = min(accessible_L, accessible_R), outside cells: periodic wrap / OPEN 1 / CLOSED 0), bit 6 = active.

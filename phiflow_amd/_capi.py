@@ -32,6 +32,7 @@ EXPORTED_SYMBOLS = (
     "phihip_slab_residual", "phihip_slab_matvec", "phihip_slab_update", "phihip_slab_state", "phihip_set_small_grid_solver",
     "phihip_grid_sample", "phihip_grid_sample_backward", "phihip_set_deferred_x_update", "phihip_set_advect_halo", "phihip_advect_fallback_stats", "phihip_set_advect_chunk", "phihip_set_advect_windows_2d", "phihip_query_advect_chunk", "phihip_set_autotune", "phihip_allreduce_residual", "phihip_set_single_reduction_cg", "phihip_set_resident_cg", "phihip_set_advect_dma", "phihip_workspace_placement",
     "phihip_diffuse_explicit_centered_coef", "phihip_diffuse_implicit_centered_coef",
+    "phihip_advect_centered_vector", "phihip_staggered_to_centered", "phihip_centered_vector_to_staggered",
 )
 
 
@@ -240,6 +241,11 @@ class Library:
         d.phihip_set_resident_cg.argtypes = [c_void_p, c_int, ctypes.c_longlong]
         d.phihip_allreduce_residual.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]
         d.phihip_advect_fallback_stats.argtypes = [c_void_p, POINTER(c_int32 * 2), c_void_p]
+        d.phihip_advect_centered_vector.argtypes = [c_void_p, POINTER(Grid), c_void_p, c_int, c_int, POINTER((c_int32 * 2) * 3),
+                                                    POINTER((c_double * 2) * 3), c_void_p, c_int, c_void_p, c_double, c_void_p]
+        d.phihip_staggered_to_centered.argtypes = [c_void_p, POINTER(Grid), POINTER(_Ptr3), c_void_p, c_void_p]
+        d.phihip_centered_vector_to_staggered.argtypes = [c_void_p, POINTER(Grid), c_void_p, c_int, POINTER((c_int32 * 2) * 3),
+                                                          POINTER((c_double * 2) * 3), POINTER(_Ptr3), c_void_p]
         d.phihip_query_plan.argtypes = [c_void_p, POINTER(Grid), c_int, c_int, POINTER(c_int32 * 6)]
         for name in EXPORTED_SYMBOLS:
             if name not in ("phihip_version", "phihip_last_error", "phihip_build_id"):
@@ -319,6 +325,23 @@ class Context:
         bc, val = self._scalar_bc(grid, s_bc, s_val)
         self.lib.check(self.lib.dll.phihip_advect_centered(self.handle, ctypes.byref(grid), s, ctypes.byref(bc), ctypes.byref(val),
                                                            ctypes.byref(ptr3(velocity)), out, float(dt), stream or None))
+
+    def advect_centered_vector(self, grid, field, field_batch, components, s_bc, s_val, velocity, velocity_batch, out, dt, stream=0):
+        """ centred field (field_batch, components, *res) advected by a centred velocity (velocity_batch, rank, *res) on the same grid """
+        bc, val = self._scalar_bc(grid, s_bc, s_val)
+        self.lib.check(self.lib.dll.phihip_advect_centered_vector(self.handle, ctypes.byref(grid), field, int(field_batch), int(components),
+                                                                  ctypes.byref(bc), ctypes.byref(val), velocity, int(velocity_batch), out,
+                                                                  float(dt), stream or None))
+
+    def staggered_to_centered(self, grid, velocity, out, stream=0):
+        """ staggered components -> cell centres, out (batch, rank, *res) """
+        self.lib.check(self.lib.dll.phihip_staggered_to_centered(self.handle, ctypes.byref(grid), ctypes.byref(ptr3(velocity)), out, stream or None))
+
+    def centered_vector_to_staggered(self, grid, field, field_batch, s_bc, s_val, out, stream=0):
+        """ centred vector (field_batch, rank, *res) -> the stored faces of `grid` """
+        bc, val = self._scalar_bc(grid, s_bc, s_val)
+        self.lib.check(self.lib.dll.phihip_centered_vector_to_staggered(self.handle, ctypes.byref(grid), field, int(field_batch), ctypes.byref(bc),
+                                                                        ctypes.byref(val), ctypes.byref(ptr3(out)), stream or None))
 
     def grid_sample(self, grid, values, values_batch, coords, points, out, out_min=0, out_max=0, stream=0):
         """ math.grid_sample: `grid` describes the VALUES array (res = its shape, bc / bc_val[..][0] = its extrapolation) """

@@ -1,7 +1,8 @@
 """
 Advection schemes backed by libphihip (reference: phi/physics/advect.py).
 Implemented on the HIP backend: `semi_lagrangian` / `advect` / `mac_cormack` with the `euler` (fused kernels) and `rk4` / `finite_rk4` integrators for StaggeredGrid
-and CenteredGrid fields advected by a StaggeredGrid velocity. Anything else raises `NotImplementedError`.
+and CenteredGrid fields advected by a StaggeredGrid velocity, and for centred scalar / vector fields advected by a centred vector velocity (Burgers'
+equation: `advect.semi_lagrangian(v, v, dt)` of a CenteredGrid). Anything else raises `NotImplementedError`.
 """
 from typing import Callable
 
@@ -34,7 +35,8 @@ def semi_lagrangian(field: Field, velocity: Field, dt: float, integrator: Callab
 
     Args:
         field: quantity to be advected (`StaggeredGrid` or `CenteredGrid`)
-        velocity: `StaggeredGrid`; on the same grid the fused kernels run, otherwise the general sampling path (sampling.py)
+        velocity: `StaggeredGrid`, or a centred vector `CenteredGrid` for a centred field; on the same grid the fused kernels run, otherwise
+            the general sampling path (sampling.py)
         dt: time increment
         integrator: `euler` (fused kernels), `rk4` or `finite_rk4` (general sampling path)
 
@@ -57,9 +59,11 @@ def _advect(field: Field, velocity: Field, dt: float, integrator: Callable, corr
     require_plain(field, 'advect'); require_plain(velocity, 'advect (velocity)')
     if integrator not in (euler, rk4, finite_rk4):
         raise NotImplementedError("HIP backend: grid advection supports the integrators euler, rk4 and finite_rk4")
-    if not velocity.is_staggered:
-        raise NotImplementedError("HIP backend: the advecting velocity must be a StaggeredGrid")
     from . import sampling
+    if velocity.is_centered:
+        return _advect_by_centered(field, velocity, dt, integrator, correction_strength)
+    if field.is_vector:     # a centred vector field by a staggered velocity: gathers at explicit coordinates
+        return sampling.advect_general(field, velocity, float(dt), correction_strength, integrator.__name__)
     if integrator is not euler:   # Runge-Kutta back-trace: explicit velocity evaluations at the intermediate points
         return sampling.advect_general(field, velocity, float(dt), correction_strength, integrator.__name__)
     if not sampling.same_grid(field, velocity):
@@ -100,6 +104,37 @@ def _advect(field: Field, velocity: Field, dt: float, integrator: Callable, corr
     else:
         be.ctx.mac_cormack_centered(grid, src.data_ptr(), s_codes, s_val, _ptrs(vel), out.data_ptr(), dt, correction_strength, be.stream())
     return Field(field.resolution, field.bounds, field.boundary, out, False, be, field.batched or velocity.batched)
+
+
+def _advect_by_centered(field: Field, velocity: Field, dt: float, integrator: Callable, correction_strength) -> Field:
+    """ a centred scalar or vector field advected by a centred vector velocity. euler, same grid, no gradient: one launch of
+    `phihip_advect_centered_vector` (the velocity at the cell is the stored value, the taps are shared by the components); everything else
+    through the general sampling path, which differentiates through GridSample. """
+    from . import sampling
+    from .field import _centered_rule, _torch_dtype_code
+    from . import _capi
+    if field.is_staggered:
+        raise NotImplementedError("HIP backend: advecting a StaggeredGrid by a centred velocity is not implemented; pass the StaggeredGrid "
+                                  "velocity (`StaggeredGrid(v, ...)`) or advect a CenteredGrid")
+    if not velocity.is_vector:
+        raise NotImplementedError("HIP backend: the advecting velocity is a centred SCALAR field; pass a vector field (StaggeredGrid or a "
+                                  "CenteredGrid with a vector axis)")
+    assert field.dtype == velocity.dtype, "field and velocity must have the same precision"
+    fused = integrator is euler and correction_strength is None and sampling.same_grid(field, velocity) \
+        and not autodiff.needs_grad(field.values, velocity.values)
+    if not fused:
+        return sampling.advect_general(field, velocity, float(dt), correction_strength, integrator.__name__)
+    be = field.backend
+    s_codes, s_val = _centered_rule(field, 'advect')
+    B = max(field.batch_size, velocity.batch_size)
+    D = field.spatial_rank
+    C = D if field.is_vector else 1
+    src = field.values.contiguous()
+    vel = src if field is velocity else velocity.values.contiguous()
+    grid = _capi.make_grid(D, _torch_dtype_code(field.dtype), B, list(field.resolution.values()), field.bounds.lower, field.bounds.upper, s_codes)
+    out = torch.empty((B,) + tuple(src.shape[1:]), dtype=src.dtype, device=src.device)
+    be.ctx.advect_centered_vector(grid, src.data_ptr(), src.shape[0], C, s_codes, s_val, vel.data_ptr(), vel.shape[0], out.data_ptr(), dt, be.stream())
+    return Field(field.resolution, field.bounds, field.boundary, out, False, be, field.batched or velocity.batched, vector=field.is_vector)
 
 
 def advect(field: Field, velocity: Field, dt: float, integrator: Callable = euler) -> Field:

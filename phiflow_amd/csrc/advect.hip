@@ -371,3 +371,5 @@ int run_grid_sample(phihip_ctx* ctx, const GridView& v, const int32_t s_bc[3][2]
 }
 
 }  // namespace phihip
+
+#include "advect_cvec.hpp"     // centred vector fields: fused advection, staggered <-> centres

@@ -540,6 +540,56 @@ int phihip_centered_to_staggered(phihip_ctx* ctx, const phihip_grid* grid, const
     return run_centered_to_staggered(ctx, v, sfield, s_bc, s_val, vec, accumulate, o, s);
 }
 
+// A centred field's grid: the view of a copy whose non-periodic sides are OPEN (no face bookkeeping: a centred field with one cell between
+// two constant sides is fine); the field's own rule comes in s_bc / s_val. Unlike sampler_view the bounds (cell sizes) are kept.
+static int centered_view(const phihip_grid* grid, phihip_grid* plain) {
+    PHIHIP_REQUIRE(grid != nullptr, "grid is NULL");
+    *plain = *grid;
+    for (int d = 0; d < 3 && d < grid->rank; ++d)
+        for (int side = 0; side < 2; ++side)
+            if (grid->bc[d][side] != PHIHIP_BC_PERIODIC) plain->bc[d][side] = PHIHIP_BC_OPEN;
+    return PHIHIP_OK;
+}
+
+int phihip_advect_centered_vector(phihip_ctx* ctx, const phihip_grid* grid_in, const void* field, int field_batch, int components,
+                                  const int32_t s_bc[3][2], const double s_val[3][2], const void* velocity, int velocity_batch, void* out,
+                                  double dt, void* stream) {
+    phihip_grid plain;
+    PHIHIP_TRY(centered_view(grid_in, &plain));
+    const phihip_grid* grid = &plain;
+    PHIHIP_ENTER(ctx, grid);
+    PHIHIP_REQUIRE(field && velocity && out && s_bc, "advect_centered_vector: NULL argument");
+    PHIHIP_REQUIRE(components >= 1 && components <= 16, "advect_centered_vector: components must be in 1..16 (got %d)", components);
+    PHIHIP_REQUIRE(field_batch == 1 || field_batch == v.batch, "advect_centered_vector: field_batch must be 1 or grid.batch");
+    PHIHIP_REQUIRE(velocity_batch == 1 || velocity_batch == v.batch, "advect_centered_vector: velocity_batch must be 1 or grid.batch");
+    PHIHIP_REQUIRE(out != field && out != velocity, "advect_centered_vector: out must not alias an input");
+    PHIHIP_TRY(check_scalar_bc(v, s_bc, "advect_centered_vector"));
+    return run_advect_cvec(ctx, v, field, field_batch, components, s_bc, s_val, velocity, velocity_batch, out, dt, s);
+}
+
+int phihip_staggered_to_centered(phihip_ctx* ctx, const phihip_grid* grid, const void* const velocity[3], void* out, void* stream) {
+    PHIHIP_ENTER(ctx, grid);
+    PHIHIP_REQUIRE(out != nullptr, "staggered_to_centered: out is NULL");
+    PHIHIP_TRY(check_ptrs(v, velocity, "velocity"));
+    for (int d = 0; d < v.rank; ++d) PHIHIP_REQUIRE(out != velocity[d], "staggered_to_centered: out must not alias velocity[%d]", d);
+    const void* u[3];
+    remap3(v, velocity, u);
+    return run_staggered_to_cvec(ctx, v, u, out, s);
+}
+
+int phihip_centered_vector_to_staggered(phihip_ctx* ctx, const phihip_grid* grid, const void* field, int field_batch, const int32_t s_bc[3][2],
+                                        const double s_val[3][2], void* const out[3], void* stream) {
+    PHIHIP_ENTER(ctx, grid);
+    PHIHIP_REQUIRE(field && s_bc, "centered_vector_to_staggered: NULL argument");
+    PHIHIP_REQUIRE(field_batch == 1 || field_batch == v.batch, "centered_vector_to_staggered: field_batch must be 1 or grid.batch");
+    PHIHIP_TRY(check_ptrs(v, (const void* const*)out, "out"));
+    for (int d = 0; d < v.rank; ++d) PHIHIP_REQUIRE(out[d] != field, "centered_vector_to_staggered: out[%d] must not alias the field", d);
+    PHIHIP_TRY(check_scalar_bc(v, s_bc, "centered_vector_to_staggered"));
+    void* o[3];
+    remap3w(v, out, o);
+    return run_cvec_to_faces(ctx, v, field, field_batch, s_bc, s_val, o, s);
+}
+
 static_assert(sizeof(phihip_obstacle) == 4 * 4 + 8 * 21, "phihip_obstacle layout is part of the ABI (phiflow_amd/_capi.py mirrors it)");
 static_assert(sizeof(phihip_solve) == 32 && sizeof(phihip_solve_info) == 32, "ABI structs");
 

@@ -331,6 +331,12 @@ int run_mac_cormack_staggered(phihip_ctx*, const GridView&, const void* const f[
                               double strength, hipStream_t);
 int run_mac_cormack_centered(phihip_ctx*, const GridView&, const void* s, const int32_t s_bc[3][2], const double s_val[3][2],
                              const void* const v[3], void* out, double dt, double strength, hipStream_t);
+// centred vector fields (advect_cvec.hpp, compiled through advect.hip)
+int run_advect_cvec(phihip_ctx*, const GridView&, const void* field, int field_batch, int C, const int32_t s_bc[3][2], const double s_val[3][2],
+                    const void* vel, int vel_batch, void* out, double dt, hipStream_t);
+int run_staggered_to_cvec(phihip_ctx*, const GridView&, const void* const vel[3], void* out, hipStream_t);
+int run_cvec_to_faces(phihip_ctx*, const GridView&, const void* field, int field_batch, const int32_t s_bc[3][2], const double s_val[3][2],
+                      void* const out[3], hipStream_t);
 int run_centered_to_staggered(phihip_ctx*, const GridView&, const void* s, const int32_t s_bc[3][2], const double s_val[3][2],
                               const double vector[3], int accumulate, void* const out[3], hipStream_t);
 int run_obstacle_accessible(phihip_ctx*, const GridView&, const phihip_obstacle* obs, int count, uint8_t* accessible, hipStream_t);

@@ -20,6 +20,27 @@ def _scalar_walls(f: Field):
     return codes, val
 
 
+def _fold(u: Field, diffusivity, what: str):
+    """ a centred vector field (B, C, *res) as the centred scalar field (B * C, *res) -- a free view -- and its diffusivity with a Field of
+    batch B expanded to B * C (entry b * C + c diffuses component c of batch entry b) """
+    from .field import require_scalar_boundary
+    require_scalar_boundary(u.boundary, u.dims, what)
+    B, C = u.batch_size, u.spatial_rank
+    folded = Field(u.resolution, u.bounds, u.boundary, u.values.reshape(B * C, *u.values.shape[2:]), False, u.backend, True)
+    if isinstance(diffusivity, Field) and diffusivity.is_centered and not diffusivity.is_vector and diffusivity.batch_size > 1:
+        if diffusivity.batch_size != B:
+            raise NotImplementedError(f"{what}: a diffusivity with batch {diffusivity.batch_size} for a field with batch {B}")
+        diffusivity = Field(diffusivity.resolution, diffusivity.bounds, diffusivity.boundary, diffusivity.values.repeat_interleave(C, dim=0), False,
+                            diffusivity.backend, True, diffusivity.vector_scale)
+    return folded, diffusivity
+
+
+def _unfold(u: Field, result: Field) -> Field:
+    out = Field(u.resolution, u.bounds, u.boundary, result.values.reshape(u.values.shape), False, u.backend, u.batched, vector=True)
+    out.solve_info = result.solve_info
+    return out
+
+
 def _diffusivity(u: Field, diffusivity, what: str):
     """ -> (None, k) for a number (the constant-coefficient path), else (coefficient Field on u's grid or None, per-axis factors [D]).
     A Field that does not live on u's grid is resampled first (`amount.at(u)`, diffuse.py:55-56), keeping its own extrapolation. """
@@ -70,6 +91,9 @@ def explicit(u: Field, diffusivity, dt: float, substeps: int = 1, order: int = 2
     flux form of diffuse.py:129-141. """
     from .field import require_plain
     require_plain(u, 'diffuse.explicit')
+    if u.is_vector:         # a centred vector field: every component is a centred scalar grid, diffused on its own (DESIGN.md f1d)
+        folded, folded_k = _fold(u, diffusivity, 'diffuse.explicit')
+        return _unfold(u, explicit(folded, folded_k, dt, substeps, order))
     if order != 2:
         raise NotImplementedError("HIP backend: diffuse.explicit implements order=2 only")
     coef, k = _diffusivity(u, diffusivity, 'diffuse.explicit')
@@ -156,6 +180,9 @@ def implicit(field: Field, diffusivity, dt: float, solve=None, order: int = 2) -
     operator does not couple them). `solve`: `Solve('CG' | 'CG-adaptive', rel_tol, abs_tol, max_iterations)`; raises
     `NotConverged` / `Diverged` like `solve_linear` unless suppressed. Differentiable w.r.t. the field: the operator is symmetric, the
     backward pass is one more solve (with `solve.gradient_solve` if given) of the same system with homogeneous boundary constants.
+    A centred VECTOR field is solved as one CG per (batch entry, component) on the (B * C, *res) view; its SolveInfo lists them batch-major.
+    PhiML solves the stacked vector as one system: per-component convergence (|r_c| <= rel |y_c| for every c) implies the joint criterion,
+    so a converged result passes the reference's stopping test, but the iterates (and the iteration counts) differ.
     `diffusivity` takes the forms of `explicit`; a Field or per-axis one runs the CG of csrc/diffuse_coef.hpp on sharpen = I + L_{-dt a}. """
     from .field import require_plain, _torch_dtype_code
     from .solve import Solve, SolveInfo
@@ -164,6 +191,9 @@ def implicit(field: Field, diffusivity, dt: float, solve=None, order: int = 2) -
     from .fluid import _raise_if_failed
     from . import _capi
     require_plain(field, 'diffuse.implicit')
+    if field.is_vector:     # one CG per (batch entry, component); SolveInfo lists them batch-major (entry b * C + c)
+        folded, folded_k = _fold(field, diffusivity, 'diffuse.implicit')
+        return _unfold(field, implicit(folded, folded_k, dt, solve, order))
     if order != 2:
         raise NotImplementedError("HIP backend: diffuse.implicit implements order=2 only")
     solve = Solve('CG') if solve is None else solve

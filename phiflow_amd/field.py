@@ -3,7 +3,8 @@
 (reference: phi/field/_field.py:51-211, phi/field/_grid.py:21-176, phi/geom/_grid.py:41-122,204-209).
 
 Only uniform grids are supported. A field owns device tensors (torch, ROCm) laid out exactly as the C ABI wants them:
-  * CenteredGrid  -> one tensor (batch, x, y[, z])
+  * CenteredGrid  -> one tensor (batch, x, y[, z]); a centred VECTOR field (`is_vector`) -> one tensor (batch, D, x, y[, z]), component-major:
+    component c of batch entry b is a contiguous centred scalar grid, so (batch * D, *res) is a free view for the scalar kernels
   * StaggeredGrid -> one tensor per component d with shape (batch, *res + (lo+up-1) e_d)   (faces stored iff
     `boundary.valid_outer_faces(d)`, tests/commit/field/test__grid.py:25-36)
 Fields are immutable from the user's point of view: every operator returns new fields (phi/field/_field.py:49-51).
@@ -17,7 +18,8 @@ import torch
 from . import _capi
 from .backend import HipBackend, default_backend, float_dtype
 from .extrapolation import BOUNDARY, PERIODIC, ZERO, ConstantExtrapolation, Extrapolation, as_extrapolation, resolve
-from .geom import Box, Geometry
+from .geom import Box, Geometry, Vector
+from .noise import Noise
 
 
 def _torch_dtype_code(dtype: torch.dtype) -> int:
@@ -32,16 +34,18 @@ _GRID_CACHE = {}      # (id of the resolved boundary codes, dtype, batch, resolu
 
 
 class Field:
-    """ A sampled scalar (centred) or vector (staggered) grid field with boundary conditions. """
+    """ A sampled grid field with boundary conditions: a centred scalar, a centred vector (`is_vector`) or a staggered vector. """
     __array_ufunc__ = None     # `numpy_array * field` defers to Field.__rmul__ (a batch vector, one number per batch entry)
     solve_info = None          # set on the pressure that a solve returns (solve.SolveInfo); None on every other field and on results of a captured function (jit.py)
 
     def __init__(self, resolution: Dict[str, int], bounds: Box, boundary: Extrapolation, values, staggered: bool,
-                 backend: HipBackend, batched: bool, vector_scale: Optional[Sequence[float]] = None):
+                 backend: HipBackend, batched: bool, vector_scale: Optional[Sequence[float]] = None, vector: bool = False):
         # vector_scale: `scalar * (0, 0.1)` -- a centred scalar times a constant vector, kept lazily (values stay the scalar's) until
         # it is resampled to a staggered grid with `@` / `resample`. Arithmetic and resample carry it along; every other consumer of
         # `values` (mean, gradients, divergence, advection, diffusion, losses, file output) calls `require_plain` and refuses
-        assert vector_scale is None or (not staggered and len(vector_scale) == len(resolution))
+        assert vector_scale is None or (not staggered and not vector and len(vector_scale) == len(resolution))
+        assert not (vector and staggered)
+        self.is_vector = bool(vector)      # centred vector field: values (batch, D, *res)
         self.vector_scale = [float(c) for c in vector_scale] if vector_scale is not None else None
         self.resolution = dict(resolution)
         self._dims = tuple(self.resolution)
@@ -112,14 +116,20 @@ class Field:
 
     # --- access ---------------------------------------------------------------------------------------------------
     def numpy(self):
-        """ host copy; batch dim squeezed when the field is not batched. Staggered: list of component arrays. """
+        """ host copy; batch dim squeezed when the field is not batched. Staggered: list of component arrays. Centred vector: channel-last
+        (*res, D) like the constructor takes it (PhiML's order: spatial, then vector). """
         def conv(t):
             a = t.detach().cpu().numpy()
             return a if self.batched else a[0]
+        if self.is_vector:
+            return conv(torch.movedim(self.values, 1, -1))
         return [conv(t) for t in self.values] if self.is_staggered else conv(self.values)
 
     def __getitem__(self, item) -> 'Field':
-        """ `v['x']`: component as a centred field on its staggered sub-grid (phi/field/_field.py:657-689) """
+        """ `v['x']`: component as a centred field on its staggered sub-grid (phi/field/_field.py:657-689); of a centred vector field the
+        component as a centred scalar field on the same grid """
+        if self.is_vector and item in self.dims:
+            return Field(self.resolution, self.bounds, self.boundary, self.values[:, self.dims.index(item)], False, self.backend, self.batched)
         assert self.is_staggered and item in self.dims, f"can only select a vector component of a staggered field, got {item!r}"
         d = self.dims.index(item)
         lo, up = self.boundary.valid_outer_faces(item)
@@ -132,7 +142,7 @@ class Field:
         return Field(res, Box(**kw), comp_boundary, self.values[d], False, self.backend, self.batched)
 
     def with_values(self, values) -> 'Field':
-        return Field(self.resolution, self.bounds, self.boundary, values, self.is_staggered, self.backend, self.batched, self.vector_scale)
+        return Field(self.resolution, self.bounds, self.boundary, values, self.is_staggered, self.backend, self.batched, self.vector_scale, self.is_vector)
 
     def with_boundary(self, boundary) -> 'Field':
         """ change the extrapolation; staggered fields re-store their boundary faces accordingly: faces that become
@@ -140,7 +150,7 @@ class Field:
         (phi/field/_field.py:451-472; tests/commit/field/test__grid.py:85-94). """
         boundary = as_extrapolation(boundary)
         if not self.is_staggered:
-            return Field(self.resolution, self.bounds, boundary, self.values, False, self.backend, self.batched, self.vector_scale)
+            return Field(self.resolution, self.bounds, boundary, self.values, False, self.backend, self.batched, self.vector_scale, self.is_vector)
         new_vals = []
         for d, dim in enumerate(self.dims):
             t = self.values[d]
@@ -169,6 +179,17 @@ class Field:
     def _op(self, other, fn, additive: bool = False) -> 'Field':
         """ elementwise `fn(self, other)`. additive: + / - (a lazy `scalar * vector` field only combines with one of the same vector) """
         scale = self.vector_scale
+        vector = self.is_vector
+        if isinstance(other, Field) and (self.is_vector or other.is_vector):
+            # centred vector with a centred vector, or with a centred scalar (broadcast over the components)
+            assert self.is_centered and other.is_centered and same_grid(self, other), \
+                f"incompatible fields (sample points differ): {self!r} vs {other!r}; resample one with `@` first"
+            if self.vector_scale is not None or other.vector_scale is not None:
+                raise NotImplementedError("combining a centred vector field with a lazy `scalar * vector` field; resample it with "
+                                          "`field @ vector_field` first")
+            a = self.values if self.is_vector else self.values.unsqueeze(1)
+            b = other.values if other.is_vector else other.values.unsqueeze(1)
+            return Field(self.resolution, self.bounds, self.boundary, fn(a, b), False, self.backend, self.batched or other.batched, None, True)
         if isinstance(other, Field):
             assert other.is_staggered == self.is_staggered and same_grid(self, other), \
                 f"incompatible fields (sample points differ): {self!r} vs {other!r}; resample one with `@` first"
@@ -184,6 +205,11 @@ class Field:
             else:
                 vals = fn(self.values, other.values)
             batched = self.batched or other.batched
+        elif isinstance(other, (tuple, list)) and self.is_vector:
+            assert len(other) == self.spatial_rank, f"vector operand of length {len(other)} for a {self.spatial_rank}-D vector field"
+            w = torch.as_tensor([float(c) for c in other], dtype=self.dtype, device=self.backend.device).reshape(1, -1, *([1] * self.spatial_rank))
+            vals = fn(self.values, w)
+            batched = self.batched
         elif isinstance(other, (tuple, list)):
             assert self.is_staggered and len(other) == self.spatial_rank, "vector operand requires a staggered field"
             vals = [fn(a, float(c)) for a, c in zip(self.values, other)]
@@ -194,20 +220,20 @@ class Field:
             # one number per batch entry, e.g. `inflow_rate * resample(inflow, to=s, soft=True)` (Batched_Smoke.ipynb)
             assert self.batch_size in (1, len(other)), f"batch vector of length {len(other)} does not match batch size {self.batch_size}"
             w = torch.as_tensor(np.asarray(other) if isinstance(other, np.ndarray) else other, dtype=self.dtype, device=self.backend.device)
-            w = w.reshape(-1, *([1] * self.spatial_rank))
+            w = w.reshape(-1, *([1] * (self.spatial_rank + int(self.is_vector))))
             vals = [fn(a, w) for a in self.values] if self.is_staggered else fn(self.values, w)
             batched = True
         else:
             vals = [fn(a, other) for a in self.values] if self.is_staggered else fn(self.values, other)
             batched = self.batched
-        return Field(self.resolution, self.bounds, self.boundary, vals, self.is_staggered, self.backend, batched, scale)
+        return Field(self.resolution, self.bounds, self.boundary, vals, self.is_staggered, self.backend, batched, scale, vector)
 
     def __add__(self, other): return self._op(other, lambda a, b: a + b, additive=True)
     def __radd__(self, other): return self._op(other, lambda a, b: b + a, additive=True)
     def __sub__(self, other): return self._op(other, lambda a, b: a - b, additive=True)
     def __rsub__(self, other): return self._op(other, lambda a, b: b - a, additive=True)
     def __mul__(self, other):
-        if isinstance(other, (tuple, list)) and self.is_centered:
+        if isinstance(other, (tuple, list)) and self.is_centered and not self.is_vector:
             return vector_scaled(self, other)   # `smoke * (0, 0.1)`; becomes a vector field when resampled with `@`
         return self._op(other, lambda a, b: a * b)
 
@@ -218,13 +244,21 @@ class Field:
         return self._op(other, lambda a, b: a / b)
     def __neg__(self): return self._op(-1.0, lambda a, b: a * b)
 
+    def at_centers(self) -> 'Field':
+        """ `field.at_centers()`: the field sampled at the cell centres of its grid -- a centred vector field for a staggered one
+        (phi/field/_field.py, _resample.py:241-259), the field itself when it is centred """
+        if self.is_centered:
+            return self
+        target = torch.zeros((1,) + tuple(self.resolution.values()), dtype=self.dtype, device=self.backend.device)
+        return resample(self, to=Field(self.resolution, self.bounds, self.boundary, target, False, self.backend, False))
+
     def __matmul__(self, other: 'Field') -> 'Field':
         """ `value @ target`: resample to the sample points of `target`, keeping `target`'s boundary
         (phi/field/_field.py `__matmul__` -> resample). """
         return resample(self, to=other)
 
     def __repr__(self):
-        kind = "StaggeredGrid" if self.is_staggered else "CenteredGrid"
+        kind = "StaggeredGrid" if self.is_staggered else ("CenteredGrid(vector)" if self.is_vector else "CenteredGrid")
         return f"{kind}[{self.resolution}, batch={self.batch_size if self.batched else None}, {self.boundary}, {self.dtype}, {self.backend}]"
 
 
@@ -234,6 +268,22 @@ def require_plain(field, what: str):
     if isinstance(field, Field) and field.vector_scale is not None:
         raise NotImplementedError(f"{what}: the field is a scalar times the constant vector {tuple(field.vector_scale)} (a centred VECTOR field, not "
                                   f"stored as such); resample it to a StaggeredGrid with `field @ velocity` / `resample(field, to=velocity)` first")
+
+
+def require_scalar_boundary(boundary: Extrapolation, dims, what: str):
+    """ a centred vector field shares ONE extrapolation among its components: vector-valued constants (`vec(x=1, y=0)`) are not implemented """
+    for d in dims:
+        for upper in (False, True):
+            side = boundary.side(d, upper)
+            if isinstance(side, ConstantExtrapolation) and isinstance(side.value, (dict, tuple, list)):
+                raise NotImplementedError(f"{what}: a vector-valued constant extrapolation ({side}) of a centred vector field is not implemented; "
+                                          f"use a number, ZERO_GRADIENT or PERIODIC")
+
+
+def require_centered_scalar(field, what: str):
+    """ refuse a centred vector field where only scalars (or staggered vectors) are implemented """
+    if isinstance(field, Field) and field.is_vector:
+        raise NotImplementedError(f"{what} of a centred vector field (CenteredGrid with a vector axis) is not implemented")
 
 
 def same_grid(a: 'Field', b: 'Field') -> bool:
@@ -314,39 +364,92 @@ def _tensor_from(value, spatial_shape, backend: HipBackend, dtype) -> Tuple[torc
     return backend.as_tensor(np.ascontiguousarray(arr), dtype), batched
 
 
+def _is_number_vector(values, D: int) -> bool:
+    return isinstance(values, (tuple, list)) and len(values) == D and all(isinstance(v, (int, float)) for v in values)
+
+
+def _vector_tensor_from(value, spatial_shape, backend: HipBackend, dtype) -> Tuple[torch.Tensor, bool]:
+    """ an array / tensor with a trailing vector axis, (*res, D) or (batch, *res, D) -> (batch, D, *res), batched """
+    D = len(spatial_shape)
+    t = value.to(device=backend.device, dtype=dtype) if isinstance(value, torch.Tensor) else backend.as_tensor(np.ascontiguousarray(value, dtype=np.float64), dtype)
+    if tuple(t.shape) == tuple(spatial_shape) + (D,):
+        return torch.movedim(t, -1, 0).unsqueeze(0).contiguous(), False
+    assert t.dim() == D + 2 and tuple(t.shape[1:]) == tuple(spatial_shape) + (D,), \
+        f"values of shape {tuple(t.shape)} match neither (batch?, *{spatial_shape}) nor (batch?, *{spatial_shape}, {D})"
+    return torch.movedim(t, -1, 1).contiguous(), True
+
+
+def _fits_scalar(value, spatial_shape) -> bool:
+    shp = tuple(np.shape(value)) if not isinstance(value, torch.Tensor) else tuple(value.shape)
+    return shp == tuple(spatial_shape) or (len(shp) == len(spatial_shape) + 1 and shp[1:] == tuple(spatial_shape)) or len(shp) == 0
+
+
 def CenteredGrid(values=0., boundary=0., bounds: Optional[Box] = None, resolution: Optional[Dict[str, int]] = None,
                  batch: Optional[int] = None, backend: Optional[HipBackend] = None, **resolution_) -> Field:
     """ `CenteredGrid(values, boundary, bounds, x=.., y=..)` (phi/field/_grid.py:21-86).
-    values: number | array/tensor (optionally with leading batch dim) | callable(*coords) | Geometry (hard mask) | Field """
+    values: number | array/tensor (optionally with leading batch dim) | callable(*coords) | Geometry (hard mask) | Field | Noise.
+    Centred VECTOR fields from: a tuple / list of D numbers or `vec(x=.., y=..)` | a callable returning `vec(x=array, y=array)` | an
+    array / tensor with a trailing vector axis (*res, D) or (batch, *res, D) (an array that also fits (batch, *res) keeps that meaning) |
+    `Noise(vector='x,y')` | a StaggeredGrid on the same grid (`at_centers`). """
     backend = backend or default_backend()
     boundary = as_extrapolation(boundary)
     res, bounds = _resolve_grid_args(bounds, resolution, resolution_)
     shape = tuple(res.values())
+    D = len(shape)
     dtype = float_dtype()
-    if isinstance(values, Field):
+    vector = False
+    if isinstance(values, Field) and values.is_staggered:
+        assert values.resolution == res
+        target = Field(res, bounds, boundary, torch.zeros((1,) + shape, dtype=values.dtype, device=backend.device), False, backend, False)
+        t = resample(values, to=target)
+        t, batched, vector = t.values.to(dtype), t.batched, True
+    elif isinstance(values, Field):
         assert values.is_centered and values.resolution == res
-        t, batched = values.values.to(dtype), values.batched
+        t, batched, vector = values.values.to(dtype), values.batched, values.is_vector
+    elif isinstance(values, Noise):
+        vector = values.vector is not None
+        if vector:
+            assert len(values.vector) == D, f"Noise(vector={values.vector}) on a {D}-D grid"
+        t = values.grid_sample(shape, bounds.size, D if vector else 1, backend.device, dtype, values.batch or 1)
+        t, batched = (t if vector else t[:, 0]), values.batch is not None
     elif isinstance(values, Geometry):
         pts = _sample_points(res, bounds, None, boundary)
         t, batched = _tensor_from(values.lies_inside(pts).astype(np.float64), shape, backend, dtype)
+    elif isinstance(values, Vector) or _is_number_vector(values, D):
+        comps = [values[d] for d in res] if isinstance(values, Vector) else list(values)
+        arrs = [np.broadcast_to(np.asarray(c, dtype=np.float64), shape) for c in comps]
+        t, batched, vector = backend.as_tensor(np.ascontiguousarray(np.stack(arrs)[None]), dtype), False, True
     elif callable(values):
         pts = _sample_points(res, bounds, None, boundary)
-        t, batched = _tensor_from(np.asarray(values(*pts), dtype=np.float64), shape, backend, dtype)
+        out = values(*pts)
+        if isinstance(out, Vector):         # `lambda x, y: vec(x=.., y=..)` (Variable_Boundaries.ipynb)
+            arrs = [np.asarray(out[d], dtype=np.float64) for d in res]
+            B = max([a.shape[0] for a in arrs if a.shape != shape and a.ndim == D + 1] + [1])
+            arrs = [np.broadcast_to(a if a.ndim == D + 1 else a[None], (B,) + shape) for a in arrs]
+            t, batched, vector = backend.as_tensor(np.ascontiguousarray(np.stack(arrs, axis=1)), dtype), B > 1, True
+        else:
+            t, batched = _tensor_from(np.asarray(out, dtype=np.float64), shape, backend, dtype)
     elif isinstance(values, (int, float)):
         t, batched = torch.full((1,) + shape, float(values), dtype=dtype, device=backend.device), False
+    elif not _fits_scalar(values, shape) and tuple(np.shape(values) if not isinstance(values, torch.Tensor) else values.shape)[-1:] == (D,):
+        t, batched = _vector_tensor_from(values, shape, backend, dtype)
+        vector = True
     else:
         t, batched = _tensor_from(values, shape, backend, dtype)
+    if vector and D not in (2, 3):
+        raise NotImplementedError(f"HIP backend: centred vector fields on {D}-D grids are not implemented (2-D and 3-D only)")
     if batch is not None and t.shape[0] != batch:
         assert t.shape[0] == 1
-        t, batched = t.expand(batch, *shape).contiguous(), True
-    return Field(res, bounds, boundary, t, False, backend, batched)
+        t, batched = t.expand(batch, *t.shape[1:]).contiguous(), True
+    return Field(res, bounds, boundary, t, False, backend, batched, vector=vector)
 
 
 def StaggeredGrid(values=0., boundary=0., bounds: Optional[Box] = None, resolution: Optional[Dict[str, int]] = None,
                   batch: Optional[int] = None, backend: Optional[HipBackend] = None, **resolution_) -> Field:
     """ `StaggeredGrid(values, boundary, bounds, x=.., y=..)` (phi/field/_grid.py:89-176).
     values: number | per-component tuple of numbers | list of per-component arrays/tensors | callable(*coords) returning one
-    array per component (evaluated at that component's face centres) | Geometry (hard mask at faces) | Field """
+    array per component (evaluated at that component's face centres) | Geometry (hard mask at faces) | Field (a centred vector field is
+    resampled to the faces) | Noise (every face grid sampled on its own) """
     backend = backend or default_backend()
     boundary = as_extrapolation(boundary)
     res, bounds = _resolve_grid_args(bounds, resolution, resolution_)
@@ -354,11 +457,19 @@ def StaggeredGrid(values=0., boundary=0., bounds: Optional[Box] = None, resoluti
     dtype = float_dtype()
     shapes = [component_shape(res, boundary, d) for d in range(D)]
     comps, batched = [], False
+    if isinstance(values, Field) and values.is_vector:        # centred vector -> faces
+        assert values.resolution == res
+        target = [torch.zeros((1,) + shp, dtype=values.dtype, device=backend.device) for shp in shapes]   # (lends sample points and dtype)
+        return resample(values, to=Field(res, bounds, boundary, target, True, backend, False))
     if isinstance(values, Field):
         assert values.is_staggered and values.resolution == res
         return values.with_boundary(boundary) if values.boundary != boundary else values
     for d in range(D):
-        if isinstance(values, Geometry):
+        if isinstance(values, Noise):     # every face grid sampled on its own (phi/field/_noise.py:34): cells of size dx, one per stored face
+            dx = [(bounds.upper[a] - bounds.lower[a]) / res[k] for a, k in enumerate(res)]
+            t = values.grid_sample(shapes[d], [n * h for n, h in zip(shapes[d], dx)], 1, backend.device, dtype, values.batch or 1)[:, 0]
+            b = values.batch is not None
+        elif isinstance(values, Geometry):
             pts = _sample_points(res, bounds, d, boundary)
             t, b = _tensor_from(values.lies_inside(pts).astype(np.float64), shapes[d], backend, dtype)
         elif callable(values):
@@ -406,6 +517,7 @@ def spatial_gradient(field: Field, boundary=None, at: str = 'face', order: int =
     """ `field.spatial_gradient(p, boundary, at='face')` (phi/field/_field_math.py:148-236): gradient of a centred scalar
     at the faces that a StaggeredGrid with `boundary` stores; `field.boundary` pads p. """
     require_plain(field, 'spatial_gradient')
+    require_centered_scalar(field, 'spatial_gradient')
     if at != 'face' or order != 2 or field.is_staggered:
         raise NotImplementedError("the HIP backend implements spatial_gradient(at='face', order=2) of a CenteredGrid only")
     vb = as_extrapolation(boundary if boundary is not None else field.boundary.spatial_gradient())
@@ -436,6 +548,9 @@ def mean(field: Field):
     require_plain(field, 'mean')
     if field.is_staggered:
         raise NotImplementedError
+    if field.is_vector:     # one value per component: (batch, D), or (D,) when not batched
+        m = field.values.reshape(field.batch_size, field.spatial_rank, -1).mean(dim=2)
+        return m if field.batched else m[0]
     m = field.values.reshape(field.batch_size, -1).mean(dim=1)
     return m if field.batched else m[0]
 
@@ -465,7 +580,15 @@ def resample(value, to: Field, soft: bool = False, balance: float = 0.5) -> Fiel
     if value.is_staggered == to.is_staggered and same_grid(value, to) and value.vector_scale is None:
         if value.is_staggered and value.boundary != to.boundary:
             return value.with_boundary(to.boundary)
-        return Field(value.resolution, value.bounds, to.boundary, value.values, value.is_staggered, value.backend, value.batched)
+        return Field(value.resolution, value.bounds, to.boundary, value.values, value.is_staggered, value.backend, value.batched, vector=value.is_vector)
+    if value.vector_scale is not None and to.is_vector:       # `(s * vec) @ centred_vector_target`: a real centred vector field
+        if not same_grid(value, to):
+            from . import sampling
+            return sampling.resample_general(value, to)
+        w = torch.as_tensor(value.vector_scale, dtype=value.dtype, device=value.backend.device).reshape(1, -1, *([1] * value.spatial_rank))
+        return Field(to.resolution, to.bounds, to.boundary, value.values.unsqueeze(1) * w, False, value.backend, value.batched, vector=True)
+    if (value.is_vector and to.is_staggered) or (value.is_staggered and to.is_centered):
+        return _resample_vector(value, to)
     if value.vector_scale is not None and to.is_centered:
         raise NotImplementedError("HIP backend: a `scalar * vector` field can only be resampled to a StaggeredGrid (centred vector fields "
                                   "are not implemented)")
@@ -491,6 +614,49 @@ def resample(value, to: Field, soft: bool = False, balance: float = 0.5) -> Fiel
         return Field(to.resolution, to.bounds, to.boundary, comps, True, be, value.batched or to.batched)
     from . import sampling
     return sampling.resample_general(value, to)     # different grids: one gather per (component of the) target
+
+
+def _centered_rule(field: Field, what: str):
+    """ (codes[D][2], consts[D][2]) of a centred field's extrapolation, shared by the components of a centred vector field """
+    require_scalar_boundary(field.boundary, field.dims, what)
+    codes, vals = resolve(field.boundary, field.dims)
+    consts = [[vals[a][s][0] if isinstance(field.boundary.side(d, bool(s)), ConstantExtrapolation) else 0.0 for s in range(2)]
+              for a, d in enumerate(field.dims)]
+    return codes, consts
+
+
+def _same_periodicity(a: Extrapolation, b: Extrapolation, dims) -> bool:
+    ca, cb = resolve(a, dims)[0], resolve(b, dims)[0]
+    return all((x == _capi.BC_PERIODIC) == (y == _capi.BC_PERIODIC) for pa, pb in zip(ca, cb) for x, y in zip(pa, pb))
+
+
+def _resample_vector(value: Field, to: Field) -> Field:
+    """ staggered -> cell centres (`at_centers`, phihip_staggered_to_centered) and centred vector -> stored faces
+    (phihip_centered_vector_to_staggered) on the same grid, one launch each; other grids and inputs that require grad take the general
+    sampling path (differentiable through GridSample) """
+    from . import autodiff, sampling
+    if value.spatial_rank not in (2, 3):
+        raise NotImplementedError(f"HIP backend: centred vector fields on {value.spatial_rank}-D grids are not implemented (2-D and 3-D only)")
+    src = value.values if value.is_staggered else [value.values]
+    # the face kernel pads with the centred field's own rule, so it needs the target's periodicity; otherwise (and on other grids, or with
+    # gradients) the general gather samples the field at the target's points with its extrapolation -- the same values
+    if not same_grid(value, to) or autodiff.needs_grad(*src) or (value.is_vector and not _same_periodicity(value.boundary, to.boundary, value.dims)):
+        return sampling.resample_general(value, to)
+    be = value.backend
+    B = value.batch_size
+    if value.is_staggered:          # -> centres: the velocity's own rule fills the faces that are not stored
+        vel = [t.contiguous() for t in value.values]
+        out = be.empty((B, value.spatial_rank) + tuple(value.resolution.values()), value.dtype)
+        be.ctx.staggered_to_centered(value.grid_struct(), _ptrs(vel), out.data_ptr(), be.stream())
+        return Field(to.resolution, to.bounds, to.boundary, out, False, be, value.batched, vector=True)
+    s_codes, s_val = _centered_rule(value, 'resample (centred vector -> faces)')
+    proto = Field(to.resolution, to.bounds, to.boundary, None, True, be, False)
+    grid = _capi.make_grid(value.spatial_rank, _torch_dtype_code(value.dtype), B, list(to.resolution.values()), to.bounds.lower,
+                           to.bounds.upper, proto._codes, proto._bc_val)
+    comps = [be.empty((B,) + component_shape(to.resolution, to.boundary, d), value.dtype) for d in range(value.spatial_rank)]
+    src = value.values.contiguous()
+    be.ctx.centered_vector_to_staggered(grid, src.data_ptr(), B, s_codes, s_val, _ptrs(comps), be.stream())
+    return Field(to.resolution, to.bounds, to.boundary, comps, True, be, value.batched)
 
 
 def vector_scaled(s: Field, vector: Sequence[float]) -> Field:

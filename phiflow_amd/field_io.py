@@ -88,6 +88,8 @@ def write(field: Field, file: str):
     """ Writes a (non-batched or batched) grid field to `file` in PhiFlow's .npz format. """
     from .field import require_plain
     require_plain(field, 'write')
+    if field.is_vector:
+        raise NotImplementedError("field_io.write of a centred vector field is not implemented")
     dims = list(field.dims)
     D = len(dims)
     names = (['batch'] if field.batched else []) + dims

@@ -8,6 +8,7 @@ from .autodiff import functional_gradient, gradient, jacobian, l2_loss, stop_gra
 from .backend import HipBackend, default_backend, precision, set_global_default_backend, set_global_precision
 from .extrapolation import BOUNDARY, ONE, PERIODIC, ZERO, ZERO_GRADIENT, ConstantExtrapolation, combine_sides
 from .field import CenteredGrid, Field, StaggeredGrid, assert_close, divergence, mean, resample, spatial_gradient
+from .noise import Noise
 from . import geom
 from .geom import Box, Cuboid, Sphere, embed, infinite_cylinder, union, vec
 from .fluid import Obstacle
@@ -19,7 +20,7 @@ __all__ = [
     'advect', 'diffuse', 'fluid', 'extrapolation',
     'HipBackend', 'default_backend', 'precision', 'set_global_default_backend', 'set_global_precision',
     'BOUNDARY', 'ONE', 'PERIODIC', 'ZERO', 'ZERO_GRADIENT', 'ConstantExtrapolation', 'combine_sides',
-    'CenteredGrid', 'Field', 'StaggeredGrid', 'assert_close', 'divergence', 'mean', 'resample', 'spatial_gradient',
+    'CenteredGrid', 'Field', 'StaggeredGrid', 'Noise', 'assert_close', 'divergence', 'mean', 'resample', 'spatial_gradient',
     'geom', 'Box', 'Cuboid', 'Sphere', 'embed', 'infinite_cylinder', 'union', 'vec', 'Obstacle',
     'functional_gradient', 'gradient', 'jacobian', 'l2_loss', 'stop_gradient',
     'ConvergenceException', 'Diverged', 'NotConverged', 'Solve', 'SolveInfo', 'copy_with', 'solve_linear',

@@ -211,6 +211,9 @@ def make_incompressible(velocity: Field,
     assert not correct_skew
     if order != 2:
         raise NotImplementedError("HIP backend: make_incompressible implements order=2 only")
+    if velocity.is_centered:
+        raise NotImplementedError("HIP backend: make_incompressible of a CenteredGrid velocity (the collocated wide-stencil projection) is not "
+                                  "implemented; project a StaggeredGrid (`StaggeredGrid(v, ...)`) instead")
     if not velocity.is_staggered or wide_stencil:
         raise NotImplementedError("HIP backend: make_incompressible implements the StaggeredGrid path (wide_stencil=False) only")
     if solve.method not in Solve.METHODS:
@@ -286,8 +289,16 @@ def make_incompressible(velocity: Field,
     return v_out, p_out
 
 
+def _require_staggered_velocity(velocity: Field, what: str):
+    """ obstacles meet staggered velocities only: the kernels take one array per face component """
+    if not velocity.is_staggered:
+        raise NotImplementedError(f"HIP backend: {what}: obstacles with a CenteredGrid velocity are not implemented; pass a StaggeredGrid velocity "
+                                  f"(`StaggeredGrid(v, ...)`)")
+
+
 def _apply_obstacles_in_place(velocity: Field, obstacles, values: List[torch.Tensor]):
     """ apply_boundary_conditions on contiguous component tensors; batched geometries: entry b of the batch meets obstacle entry b """
+    _require_staggered_velocity(velocity, 'apply_boundary_conditions')
     be = velocity.backend
     if _obstacle_batch(obstacles) == 1:
         be.ctx.apply_obstacles(velocity.grid_struct(), *_obstacle_array(obstacles, velocity), _ptrs(values), be.stream())
@@ -298,6 +309,7 @@ def _apply_obstacles_in_place(velocity: Field, obstacles, values: List[torch.Ten
 
 
 def _apply_obstacles_autograd(velocity: Field, obstacles, vin):
+    _require_staggered_velocity(velocity, 'apply_boundary_conditions')
     still = [Obstacle(ob.geometry) for ob in obstacles]
     arr, count = _obstacle_array(obstacles, velocity)
     meta = dict(be=velocity.backend, grid=velocity.grid_struct(), obstacles=arr, obstacles_still=_obstacle_array(still, velocity)[0], count=count,
@@ -325,6 +337,7 @@ def apply_boundary_conditions(velocity: Field, obstacles) -> Field:
     obstacles = _get_obstacles_for(obstacles, velocity)
     if not obstacles:
         return velocity
+    _require_staggered_velocity(velocity, 'apply_boundary_conditions')
     be = velocity.backend
     OB = _obstacle_batch(obstacles)
     if autodiff.needs_grad(*velocity.values):

@@ -68,20 +68,21 @@ def _tracing():
 # ---- argument trees: tensors out, tensors back in ---------------------------------------------------------------------------------------
 
 class _FieldSpec:
-    __slots__ = ("resolution", "bounds", "boundary", "staggered", "backend", "batched", "vector_scale", "count")
+    __slots__ = ("resolution", "bounds", "boundary", "staggered", "backend", "batched", "vector_scale", "count", "vector")
 
     def __init__(self, f: Field):
         self.resolution, self.bounds, self.boundary = dict(f.resolution), f.bounds, f.boundary
         self.staggered, self.backend, self.batched, self.vector_scale = f.is_staggered, f.backend, f.batched, f.vector_scale
         self.count = len(f.values) if f.is_staggered else 1
+        self.vector = f.is_vector           # centred vector field: values (batch, D, *res)
 
     def key(self):
         return ("Field", tuple(self.resolution.items()), repr(self.bounds), repr(self.boundary), self.staggered, id(self.backend), self.batched,
-                tuple(self.vector_scale) if self.vector_scale is not None else None)
+                tuple(self.vector_scale) if self.vector_scale is not None else None, self.vector)
 
     def build(self, tensors: List[torch.Tensor]) -> Field:
         values = list(tensors) if self.staggered else tensors[0]
-        return Field(self.resolution, self.bounds, self.boundary, values, self.staggered, self.backend, self.batched, self.vector_scale)
+        return Field(self.resolution, self.bounds, self.boundary, values, self.staggered, self.backend, self.batched, self.vector_scale, self.vector)
 
 
 class _Aux:

@@ -50,11 +50,19 @@ def _array_rule(field: Field, comp: Optional[int]):
     return codes, consts
 
 
+def _component_values(field: Field, comp: Optional[int]) -> torch.Tensor:
+    """ the array that holds a centred scalar (comp None), component `comp` of a centred vector field (batch, D, *res) or of a staggered one """
+    if comp is None:
+        return field.values
+    return field.values[:, comp] if field.is_vector else field.values[comp]
+
+
 def sample_array(field: Field, comp: Optional[int], coords: Sequence[torch.Tensor], limits: bool = False):
-    """ gathers from the array of `field` (component `comp` if staggered) at fractional index coordinates coords[d] of shape (B, points);
-    `limits`: also the min / max over the taps (Field.closest_values). Values of batch 1 are shared by all B coordinate sets. """
+    """ gathers from the array of `field` (component `comp` if staggered or a centred vector) at fractional index coordinates coords[d] of
+    shape (B, points); `limits`: also the min / max over the taps (Field.closest_values). Values of batch 1 are shared by all B coordinate
+    sets. """
     be = field.backend
-    values = (field.values if comp is None else field.values[comp]).contiguous()
+    values = _component_values(field, comp).contiguous()
     coords = [c.contiguous() for c in coords]
     B, npts = coords[0].shape
     assert values.shape[0] in (1, B), f"values batch {values.shape[0]} vs coordinates batch {B}"
@@ -95,31 +103,46 @@ def index_coords(field: Field, comp: Optional[int], points: Sequence[torch.Tenso
 
 def sample_field(field: Field, points: Sequence[torch.Tensor]) -> List[torch.Tensor]:
     """ the field's value at world points (B, n): [scalar] for a centred field, one tensor per component for a staggered one
-    (`sample(velocity, geometry)`: every component interpolated on its own staggered sub-grid) """
-    comps = [None] if field.is_centered else range(field.spatial_rank)
+    (`sample(velocity, geometry)`: every component interpolated on its own staggered sub-grid) or a centred vector field (every
+    component at the same cell-centred coordinates) """
     B = max([p.shape[0] for p in points] + [field.batch_size])
     pts = [p if p.shape[0] == B else p.expand(B, -1) for p in points]
+    if field.is_vector:
+        coords = index_coords(field, None, pts)
+        return [sample_array(field, c, coords) for c in range(field.spatial_rank)]
+    comps = [None] if field.is_centered else range(field.spatial_rank)
     return [sample_array(field, c, index_coords(field, c, pts)) for c in comps]
 
 
 
 
 def resample_general(value: Field, to: Field) -> Field:
-    """ `resample(value, to)` between different grids: centred -> centred / staggered faces (times the lazy constant vector of
-    `scalar * (0, 0.1)`), staggered -> staggered (component-wise). """
+    """ `resample(value, to)` between different grids (or on the same grid when gradients are needed): centred -> centred / staggered
+    faces (times the lazy constant vector of `scalar * (0, 0.1)`), staggered -> staggered (component-wise), staggered or centred vector ->
+    cell centres (a centred vector field), centred vector -> faces (component d at the d-faces). """
     be = to.backend
     assert value.dims == to.dims, f"fields live in different spaces: {value.dims} vs {to.dims}"
-    if value.is_staggered and to.is_centered:
-        raise NotImplementedError("HIP backend: resampling a StaggeredGrid to cell centres would need centred vector fields")
     batched = value.batched          # the target only lends its sample points
     if to.is_centered:
-        out = sample_field(value, sample_points(to))[0]
-        return Field(to.resolution, to.bounds, to.boundary, out.reshape(out.shape[0], *to.resolution.values()), False, be, batched)
+        res = tuple(to.resolution.values())
+        out = sample_field(value, sample_points(to))
+        if value.is_staggered or value.is_vector:
+            B = max(o.shape[0] for o in out)
+            vals = torch.stack([o.expand(B, -1) for o in out], dim=1).reshape(B, len(out), *res)
+            return Field(to.resolution, to.bounds, to.boundary, vals, False, be, batched, vector=True)
+        out = out[0]
+        if value.vector_scale is not None:          # `(s * vec) @ centred_vector_target`
+            w = torch.as_tensor(value.vector_scale, dtype=out.dtype, device=out.device).reshape(1, -1, *([1] * len(res)))
+            return Field(to.resolution, to.bounds, to.boundary, out.reshape(out.shape[0], 1, *res) * w, False, be, batched, vector=True)
+        return Field(to.resolution, to.bounds, to.boundary, out.reshape(out.shape[0], *res), False, be, batched)
     scale = value.vector_scale or [1.0] * value.spatial_rank
     comps = []
     for d in range(to.spatial_rank):
         pts = sample_points(to, d)
-        if value.is_centered:
+        if value.is_vector:
+            B = value.batch_size
+            t = sample_array(value, d, index_coords(value, None, [p.expand(B, -1) for p in pts]))
+        elif value.is_centered:
             t = sample_field(value, pts)[0] * scale[d]
         else:
             B = value.batch_size
@@ -152,29 +175,40 @@ def advect_general(field: Field, velocity: Field, dt: float, correction_strength
     if correction_strength is not None and field.is_staggered:
         raise NotImplementedError("HIP backend: MacCormack advection of a StaggeredGrid needs the euler integrator and the velocity on the same grid")
     comps = [None] if field.is_centered else list(range(field.spatial_rank))
+    if field.is_vector:
+        comps = list(range(field.spatial_rank))
     B = max(field.batch_size, velocity.batch_size)
     outs = []
+    back_c = ahead_c = None          # a centred vector field: all components share the cell centres, trace them once
     for c in comps:
-        pts = [p.expand(B, -1) for p in sample_points(field, c)]
-        back = integrate_points(pts, velocity, -dt, integrator)
-        if correction_strength is None:
-            new = sample_array(field, c, index_coords(field, c, back))
+        geo = None if field.is_centered else c          # which sample points / index frame (staggered components: their own faces)
+        if field.is_vector and back_c is not None:
+            pts, back = pts, back_c
         else:
-            coords_back = index_coords(field, c, back)
-            needs_grad = field.values.requires_grad or any(t.requires_grad for t in coords_back)
+            pts = [p.expand(B, -1) for p in sample_points(field, geo)]
+            back = back_c = integrate_points(pts, velocity, -dt, integrator)
+        if correction_strength is None:
+            new = sample_array(field, c, index_coords(field, geo, back))
+        else:
+            values_c = _component_values(field, c)
+            coords_back = index_coords(field, geo, back)
+            needs_grad = values_c.requires_grad or any(t.requires_grad for t in coords_back)
             with torch.no_grad():
                 fwd_vals, lo, hi = sample_array(field, c, [t.detach() for t in coords_back], limits=True)
             if needs_grad:   # differentiable gather; the clamp window stays constant (a clamped sample gets no gradient here)
                 fwd_vals = sample_array(field, c, coords_back)
             fwd = Field(field.resolution, field.bounds, field.boundary, fwd_vals.reshape(B, *field.resolution.values()), False, field.backend, True)
-            ahead = integrate_points(pts, velocity, dt, integrator)
-            bwd = sample_array(fwd, None, index_coords(fwd, None, ahead))
-            own = (field.values if field.values.shape[0] == B else field.values.expand(B, *field.values.shape[1:])).reshape(B, -1)
+            if ahead_c is None or not field.is_vector:
+                ahead_c = integrate_points(pts, velocity, dt, integrator)
+            bwd = sample_array(fwd, None, index_coords(fwd, None, ahead_c))
+            own = (values_c if values_c.shape[0] == B else values_c.expand(B, *values_c.shape[1:])).reshape(B, -1)
             new = fwd_vals + (0.5 * correction_strength) * (own - bwd)
             new = torch.minimum(torch.maximum(new, lo), hi)               # math.clip(new, min, max)
-        shape = tuple(field.resolution.values()) if c is None else component_shape(field.resolution, field.boundary, c)
+        shape = tuple(field.resolution.values()) if geo is None else component_shape(field.resolution, field.boundary, c)
         outs.append(new.reshape(B, *shape))
     batched = field.batched or velocity.batched
+    if field.is_vector:
+        return Field(field.resolution, field.bounds, field.boundary, torch.stack(outs, dim=1), False, field.backend, batched, vector=True)
     return Field(field.resolution, field.bounds, field.boundary, outs[0] if field.is_centered else outs, field.is_staggered, field.backend, batched)
 
 
