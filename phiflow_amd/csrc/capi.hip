@@ -352,21 +352,22 @@ int phihip_ctx_create(int device, phihip_ctx** out) {
     return PHIHIP_OK;
 }
 
+// every DeviceBuffer of the context: freed by phihip_ctx_destroy, counted by phihip_workspace_bytes
+static DeviceBuffer phihip_ctx::* const kCtxBuffers[] = {
+    &phihip_ctx::ws_r, &phihip_ctx::ws_d0, &phihip_ctx::ws_d1, &phihip_ctx::ws_div, &phihip_ctx::ws_part, &phihip_ctx::ws_state, &phihip_ctx::ws_scalars, &phihip_ctx::ws_rhs,
+    &phihip_ctx::ws_adv, &phihip_ctx::ws_adv_flags, &phihip_ctx::ws_adj_q, &phihip_ctx::ws_adj_l, &phihip_ctx::ws_cg1, &phihip_ctx::ws_adj_g, &phihip_ctx::ws_res, &phihip_ctx::ws_adv_const,
+    &phihip_ctx::ws_coef_r, &phihip_ctx::ws_coef_d0, &phihip_ctx::ws_coef_d1, &phihip_ctx::ws_coef_part, &phihip_ctx::ws_coef_state, &phihip_ctx::ws_coef_rhs};
+
 int phihip_ctx_destroy(phihip_ctx* ctx) {
     if (!ctx) return PHIHIP_OK;
     (void)hipSetDevice(ctx->device);
-    DeviceBuffer* bufs[] = {&ctx->ws_r, &ctx->ws_d0, &ctx->ws_d1, &ctx->ws_div, &ctx->ws_part, &ctx->ws_state, &ctx->ws_scalars, &ctx->ws_rhs, &ctx->ws_adv, &ctx->ws_adv_flags, &ctx->ws_adj_q, &ctx->ws_adj_l, &ctx->ws_cg1, &ctx->ws_adj_g, &ctx->ws_res, &ctx->ws_adv_const,
-                            &ctx->ws_coef_r, &ctx->ws_coef_d0, &ctx->ws_coef_d1, &ctx->ws_coef_part, &ctx->ws_coef_state, &ctx->ws_coef_rhs};
-    for (DeviceBuffer* b : bufs)
-        if (b->ptr) (void)hipFree(b->ptr);
-    if (ctx->host_state) (void)hipHostFree(ctx->host_state);
-    if (ctx->host_flags) (void)hipHostFree(ctx->host_flags);
+    for (auto m : kCtxBuffers)
+        if ((ctx->*m).ptr) (void)hipFree((ctx->*m).ptr);
+    cg_host_release(ctx);
     if (ctx->adv_host) (void)hipHostFree(ctx->adv_host);
     for (auto& K : ctx->adv_policy)
         for (auto& P : K.e)
             if (P.ev) (void)hipEventDestroy(P.ev);
-    for (int i = 0; i < 2; ++i)
-        if (ctx->poll_ev[i]) (void)hipEventDestroy(ctx->poll_ev[i]);
     for (auto& p : ctx->ev_pool) {
         (void)hipEventDestroy(p.a);
         (void)hipEventDestroy(p.b);
@@ -377,9 +378,8 @@ int phihip_ctx_destroy(phihip_ctx* ctx) {
 
 int phihip_workspace_bytes(const phihip_ctx* ctx, size_t* bytes) {
     PHIHIP_REQUIRE(ctx && bytes, "ctx / bytes is NULL");
-    *bytes = ctx->ws_r.bytes + ctx->ws_d0.bytes + ctx->ws_d1.bytes + ctx->ws_div.bytes + ctx->ws_part.bytes + ctx->ws_state.bytes +
-             ctx->ws_scalars.bytes + ctx->ws_rhs.bytes + ctx->ws_adv.bytes + ctx->ws_adv_flags.bytes + ctx->ws_adj_q.bytes + ctx->ws_adj_l.bytes + ctx->ws_cg1.bytes + ctx->ws_adj_g.bytes + ctx->ws_res.bytes +
-             ctx->ws_coef_r.bytes + ctx->ws_coef_d0.bytes + ctx->ws_coef_d1.bytes + ctx->ws_coef_part.bytes + ctx->ws_coef_state.bytes + ctx->ws_coef_rhs.bytes;
+    *bytes = 0;
+    for (auto m : kCtxBuffers) *bytes += (ctx->*m).bytes;
     return PHIHIP_OK;
 }
 

@@ -268,22 +268,129 @@ __global__ void cg_export_relative(const CgState* st, int batch, double* out) {
 }
 
 int run_export_relative_residual(phihip_ctx* ctx, int batch, double* out, hipStream_t s) {
-    if (!ctx->last_state || ctx->last_state_batch < batch) {
+    if (!ctx->cg.last_state || ctx->cg.last_state_batch < batch) {
         set_error("solve_relative_residual: no solve with batch >= %d has run on this context", batch);
         return PHIHIP_ERR_BAD_ARG;
     }
-    hipLaunchKernelGGL(cg_export_relative, dim3(1), dim3(kWave), 0, s, (const CgState*)ctx->last_state, batch, out);
+    hipLaunchKernelGGL(cg_export_relative, dim3(1), dim3(kWave), 0, s, ctx->cg.last_state, batch, out);
     PHIHIP_CHECK_HIP(hipGetLastError());
     return PHIHIP_OK;
 }
 
 int run_export_residuals(phihip_ctx* ctx, int batch, double* out, hipStream_t s) {
-    if (!ctx->last_state || ctx->last_state_batch < batch) {
+    if (!ctx->cg.last_state || ctx->cg.last_state_batch < batch) {
         set_error("solve_residuals: no solve with batch >= %d has run on this context", batch);
         return PHIHIP_ERR_BAD_ARG;
     }
-    hipLaunchKernelGGL(cg_export_residuals, dim3(ceil_div(batch, 64)), dim3(64), 0, s, (const CgState*)ctx->last_state, batch, out);
+    hipLaunchKernelGGL(cg_export_residuals, dim3(ceil_div(batch, 64)), dim3(64), 0, s, ctx->cg.last_state, batch, out);
     PHIHIP_CHECK_HIP(hipGetLastError());
+    return PHIHIP_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// host scaffolding shared by the CG drivers (here, cg_small.hip, cg_resident.hip, diffuse_coef.hpp): what surrounds their launches
+// ---------------------------------------------------------------------------------------------------------------------
+CgParams cg_params(const phihip_solve* solve) {
+    CgParams prm;
+    prm.rtol = solve->rel_tol; prm.atol = solve->abs_tol; prm.max_iter = solve->max_iterations; prm.pad = 0;
+    return prm;
+}
+
+// pinned readback buffer: two control blocks per batch entry
+static int grow_readback(CgHost& h, int batch) {
+    const size_t bytes = (size_t)2 * batch * sizeof(CgState);
+    if (h.host_state_bytes < bytes) {
+        if (h.host_state) (void)hipHostFree(h.host_state);
+        h.host_state = nullptr;
+        h.host_state_bytes = 0;
+        PHIHIP_CHECK_HIP(hipHostMalloc((void**)&h.host_state, bytes, hipHostMallocDefault));
+        h.host_state_bytes = bytes;
+    }
+    return PHIHIP_OK;
+}
+
+int cg_host_prepare(phihip_ctx* ctx, int batch, unsigned int* seq) {
+    CgHost& h = ctx->cg;
+    PHIHIP_TRY(grow_readback(h, batch));
+    if (!h.poll_ev[0]) {
+        PHIHIP_CHECK_HIP(hipEventCreate(&h.poll_ev[0]));
+        PHIHIP_CHECK_HIP(hipEventCreate(&h.poll_ev[1]));
+    }
+    if (h.host_flags_count < (size_t)batch) {
+        if (h.host_flags) (void)hipHostFree(h.host_flags);
+        h.host_flags = nullptr;
+        h.host_flags_count = 0;
+        PHIHIP_CHECK_HIP(hipHostMalloc((void**)&h.host_flags, (size_t)batch * sizeof(unsigned long long), hipHostMallocMapped));
+        memset(h.host_flags, 0, (size_t)batch * sizeof(unsigned long long));
+        PHIHIP_CHECK_HIP(hipHostGetDevicePointer((void**)&h.host_flags_dev, h.host_flags, 0));
+        h.host_flags_count = (size_t)batch;
+    }
+    *seq = ++h.solve_seq;   // 0 never matches: flags of earlier solves read as "still running"
+    return PHIHIP_OK;
+}
+
+void cg_host_release(phihip_ctx* ctx) {
+    CgHost& h = ctx->cg;
+    if (h.host_state) (void)hipHostFree(h.host_state);
+    if (h.host_flags) (void)hipHostFree(h.host_flags);
+    for (int i = 0; i < 2; ++i)
+        if (h.poll_ev[i]) (void)hipEventDestroy(h.poll_ev[i]);
+    h = CgHost();
+}
+
+int cg_poll(phihip_ctx* ctx, const phihip_solve* solve, int k, unsigned int seq, int batch, int* checks, hipStream_t s, bool* stop) {
+    *stop = false;
+    if (solve->check_every <= 0 || k >= solve->max_iterations) return PHIHIP_OK;
+    // Tolerance mode. Every MATVEC prologue publishes its continue decision into host-mapped memory (publish_flag), so the host
+    // looks before each enqueue -- no peek kernel, no copy -- and stops as soon as every entry reports "done" for THIS solve
+    // (sequence number). Flags only go 1 -> 0 and frozen entries make every kernel return at once, so the launches that
+    // were enqueued ahead are harmless; an event every `check_every` iterations bounds that run-ahead to two intervals.
+    CgHost& h = ctx->cg;
+    bool any = false;
+    for (int b = 0; b < batch && !any; ++b) {
+        const unsigned long long f = *(volatile unsigned long long*)(h.host_flags + b);
+        any = (unsigned int)(f >> 32) != seq || (f & 1ull);
+    }
+    if (!any) {
+        *stop = true;
+        return PHIHIP_OK;
+    }
+    if (k % solve->check_every == 0) {
+        const int slot = *checks & 1;
+        PHIHIP_CHECK_HIP(hipEventRecord(h.poll_ev[slot], s));
+        if (*checks > 0) PHIHIP_CHECK_HIP(hipEventSynchronize(h.poll_ev[slot ^ 1]));
+        ++*checks;
+    }
+    return PHIHIP_OK;
+}
+
+int cg_report(phihip_ctx* ctx, const CgState* state, int batch, phihip_solve_info* info, hipStream_t s, int flags, bool* aborted) {
+    CgHost& h = ctx->cg;
+    if (aborted) *aborted = false;
+    if (!(flags & CG_REPORT_PEEK)) {
+        h.last_state = state;
+        h.last_state_batch = batch;
+    }
+    if (!info && !(flags & CG_REPORT_SYNC)) return PHIHIP_OK;
+    PHIHIP_TRY(grow_readback(h, batch));
+    const CgState* hst = h.host_state;
+    PHIHIP_CHECK_HIP(hipMemcpyAsync(h.host_state, state, (size_t)batch * sizeof(CgState), hipMemcpyDeviceToHost, s));
+    PHIHIP_CHECK_HIP(hipStreamSynchronize(s));
+    if (aborted)
+        for (int b = 0; b < batch; ++b)
+            if (hst[b].iterations < 0) {
+                *aborted = true;
+                return PHIHIP_OK;
+            }
+    if (info)
+        for (int b = 0; b < batch; ++b) {
+            info[b].residual_sq = hst[b].rsq;
+            info[b].rhs_sq = hst[b].rhs_sq;
+            info[b].iterations = hst[b].iterations;
+            info[b].converged = hst[b].converged;
+            info[b].diverged = hst[b].diverged;
+            info[b].reserved = (flags & CG_REPORT_CONT) ? hst[b].cont : 0;
+        }
     return PHIHIP_OK;
 }
 
@@ -367,29 +474,7 @@ static int cg_small_path(phihip_ctx* ctx, const GridView& v, const uint8_t* flag
     PHIHIP_TRY(ensure_buffer(ctx->ws_state, (size_t)3 * v.batch * sizeof(CgState)));
     CgState* st = (CgState*)ctx->ws_state.ptr;
     PHIHIP_TRY(run_cg_small(ctx, v, flags, mask_batch, rhs, x, solve, st, s));
-    ctx->last_state = st;
-    ctx->last_state_batch = v.batch;
-    if (info) {
-        if (ctx->host_state_bytes < (size_t)v.batch * sizeof(CgState)) {
-            if (ctx->host_state) (void)hipHostFree(ctx->host_state);
-            ctx->host_state = nullptr;
-            ctx->host_state_bytes = 0;
-            PHIHIP_CHECK_HIP(hipHostMalloc(&ctx->host_state, (size_t)v.batch * sizeof(CgState), hipHostMallocDefault));
-            ctx->host_state_bytes = (size_t)v.batch * sizeof(CgState);
-        }
-        CgState* hst = (CgState*)ctx->host_state;
-        PHIHIP_CHECK_HIP(hipMemcpyAsync(hst, st, (size_t)v.batch * sizeof(CgState), hipMemcpyDeviceToHost, s));
-        PHIHIP_CHECK_HIP(hipStreamSynchronize(s));
-        for (int b = 0; b < v.batch; ++b) {
-            info[b].residual_sq = hst[b].rsq;
-            info[b].rhs_sq = hst[b].rhs_sq;
-            info[b].iterations = hst[b].iterations;
-            info[b].converged = hst[b].converged;
-            info[b].diverged = hst[b].diverged;
-            info[b].reserved = 0;
-        }
-    }
-    return PHIHIP_OK;
+    return cg_report(ctx, st, v.batch, info, s);
 }
 
 // 2-D fp32 grids whose iteration is bound by kernel boundaries: the whole solve in ONE launch of resident workgroups (cg_resident.hip)
@@ -410,32 +495,12 @@ static int cg_resident_path(phihip_ctx* ctx, const GridView& v, const uint8_t* f
     PHIHIP_TRY(ensure_buffer(ctx->ws_state, (size_t)4 * v.batch * sizeof(CgState)));
     CgState* st = (CgState*)ctx->ws_state.ptr;
     PHIHIP_TRY(run_cg_resident(ctx, v, flags, mask_batch, rhs, x, solve, st, shift, s));
-    ctx->last_state = st;
-    ctx->last_state_batch = v.batch;
-    if (info) {
-        if (ctx->host_state_bytes < (size_t)v.batch * sizeof(CgState)) {
-            if (ctx->host_state) (void)hipHostFree(ctx->host_state);
-            ctx->host_state = nullptr;
-            ctx->host_state_bytes = 0;
-            PHIHIP_CHECK_HIP(hipHostMalloc(&ctx->host_state, (size_t)v.batch * sizeof(CgState), hipHostMallocDefault));
-            ctx->host_state_bytes = (size_t)v.batch * sizeof(CgState);
-        }
-        CgState* hst = (CgState*)ctx->host_state;
-        PHIHIP_CHECK_HIP(hipMemcpyAsync(hst, st, (size_t)v.batch * sizeof(CgState), hipMemcpyDeviceToHost, s));
-        PHIHIP_CHECK_HIP(hipStreamSynchronize(s));
-        for (int b = 0; b < v.batch; ++b) {
-            if (hst[b].iterations < 0) {
-                if (ctx->adv_host) ctx->adv_host[15] = 0;      // (reported here)
-                set_error("cg (resident): a workgroup waited at a barrier for ~1 s -- the launch was not resident as a whole (is another stream using the device?)");
-                return PHIHIP_ERR_HIP;
-            }
-            info[b].residual_sq = hst[b].rsq;
-            info[b].rhs_sq = hst[b].rhs_sq;
-            info[b].iterations = hst[b].iterations;
-            info[b].converged = hst[b].converged;
-            info[b].diverged = hst[b].diverged;
-            info[b].reserved = 0;
-        }
+    bool aborted = false;
+    PHIHIP_TRY(cg_report(ctx, st, v.batch, info, s, 0, &aborted));
+    if (aborted) {
+        if (ctx->adv_host) ctx->adv_host[15] = 0;      // (reported here)
+        set_error("cg (resident): a workgroup waited at a barrier for ~1 s -- the launch was not resident as a whole (is another stream using the device?)");
+        return PHIHIP_ERR_HIP;
     }
     return PHIHIP_OK;
 }
@@ -851,27 +916,8 @@ static int cg1_t(phihip_ctx* ctx, const GridView& v, const uint8_t* flags, int m
     PHIHIP_TRY(ensure_buffer(ctx->ws_cg1, 4 * vec_bytes));
     PHIHIP_TRY(ensure_buffer(ctx->ws_part, 12 * part_n * sizeof(double)));
     PHIHIP_TRY(ensure_buffer(ctx->ws_state, (size_t)4 * v.batch * sizeof(CgState)));
-    if (ctx->host_state_bytes < (size_t)2 * v.batch * sizeof(CgState)) {
-        if (ctx->host_state) (void)hipHostFree(ctx->host_state);
-        ctx->host_state = nullptr;
-        ctx->host_state_bytes = 0;
-        PHIHIP_CHECK_HIP(hipHostMalloc(&ctx->host_state, (size_t)2 * v.batch * sizeof(CgState), hipHostMallocDefault));
-        ctx->host_state_bytes = (size_t)2 * v.batch * sizeof(CgState);
-    }
-    if (!ctx->poll_ev[0]) {
-        PHIHIP_CHECK_HIP(hipEventCreate(&ctx->poll_ev[0]));
-        PHIHIP_CHECK_HIP(hipEventCreate(&ctx->poll_ev[1]));
-    }
-    if (ctx->host_flags_count < (size_t)v.batch) {
-        if (ctx->host_flags) (void)hipHostFree(ctx->host_flags);
-        ctx->host_flags = nullptr;
-        ctx->host_flags_count = 0;
-        PHIHIP_CHECK_HIP(hipHostMalloc((void**)&ctx->host_flags, (size_t)v.batch * sizeof(unsigned long long), hipHostMallocMapped));
-        memset(ctx->host_flags, 0, (size_t)v.batch * sizeof(unsigned long long));
-        PHIHIP_CHECK_HIP(hipHostGetDevicePointer((void**)&ctx->host_flags_dev, ctx->host_flags, 0));
-        ctx->host_flags_count = (size_t)v.batch;
-    }
-    const unsigned int seq = ++ctx->solve_seq;
+    unsigned int seq;
+    PHIHIP_TRY(cg_host_prepare(ctx, v.batch, &seq));
     char* extra = (char*)ctx->ws_cg1.ptr;
     T* rv[2] = {(T*)ctx->ws_r.ptr, (T*)extra};
     T* wv[2] = {(T*)ctx->ws_d0.ptr, (T*)(extra + vec_bytes)};
@@ -887,8 +933,7 @@ static int cg1_t(phihip_ctx* ctx, const GridView& v, const uint8_t* flags, int m
     double* part_sg[2] = {part + 10 * part_n, part + 11 * part_n};
     CgState* st[2] = {(CgState*)ctx->ws_state.ptr, (CgState*)ctx->ws_state.ptr + v.batch};
     int cur = 0;
-    CgParams prm;
-    prm.rtol = solve->rel_tol; prm.atol = solve->abs_tol; prm.max_iter = solve->max_iterations; prm.pad = 0;
+    const CgParams prm = cg_params(solve);
     MarchArgs<T> base;
     memset(&base, 0, sizeof(base));
     base.flags = flags;
@@ -945,7 +990,7 @@ static int cg1_t(phihip_ctx* ctx, const GridView& v, const uint8_t* flags, int m
             a.part3 = part_mu[pc ^ 1]; a.part4 = part_nu[pc ^ 1]; a.part5 = part_sg[pc ^ 1];
             a.prologue = PRO_CG1;
             a.st_in = st[cur]; a.st_out = st[cur ^ 1];
-            if (solve->check_every > 0) { a.host_flags = ctx->host_flags_dev; a.seq = seq; }
+            if (solve->check_every > 0) { a.host_flags = ctx->cg.host_flags_dev; a.seq = seq; }
             LaunchScope ls(ctx, PHIHIP_K_CG_UPDATE, s);
             PHIHIP_TRY(launch_march_any<T>(v, c1, MODE_CG1, has_flags, g1, a, s));
             cur ^= 1; vc ^= 1; pc ^= 1;
@@ -957,20 +1002,9 @@ static int cg1_t(phihip_ctx* ctx, const GridView& v, const uint8_t* flags, int m
             // frozen before launch k skip both passes (PRO_CONT)
             PHIHIP_TRY(residual_and_w(PRO_CONT, false));
         }
-        if (solve->check_every > 0 && k < solve->max_iterations) {
-            bool any = false;
-            for (int b = 0; b < v.batch && !any; ++b) {
-                const unsigned long long f = *(volatile unsigned long long*)(ctx->host_flags + b);
-                any = (unsigned int)(f >> 32) != seq || (f & 1ull);
-            }
-            if (!any) break;
-            if (k % solve->check_every == 0) {
-                const int slot = checks & 1;
-                PHIHIP_CHECK_HIP(hipEventRecord(ctx->poll_ev[slot], s));
-                if (checks > 0) PHIHIP_CHECK_HIP(hipEventSynchronize(ctx->poll_ev[slot ^ 1]));
-                ++checks;
-            }
-        }
+        bool stop = false;
+        PHIHIP_TRY(cg_poll(ctx, solve, k, seq, v.batch, &checks, s, &stop));
+        if (stop) break;
     }
     {   // fold the last (gamma, delta) into the control block: converged / diverged / residual of the final iterate
         LaunchScope ls(ctx, PHIHIP_K_CG_SCALAR, s);
@@ -978,23 +1012,8 @@ static int cg1_t(phihip_ctx* ctx, const GridView& v, const uint8_t* flags, int m
                            (const double*)part_d[pc], nblk_in, prm);
         cur ^= 1;
     }
-    ctx->last_state = st[cur];
-    ctx->last_state_batch = v.batch;
     PHIHIP_CHECK_HIP(hipGetLastError());
-    if (info) {
-        CgState* hst = (CgState*)ctx->host_state;
-        PHIHIP_CHECK_HIP(hipMemcpyAsync(hst, st[cur], (size_t)v.batch * sizeof(CgState), hipMemcpyDeviceToHost, s));
-        PHIHIP_CHECK_HIP(hipStreamSynchronize(s));
-        for (int b = 0; b < v.batch; ++b) {
-            info[b].residual_sq = hst[b].rsq;
-            info[b].rhs_sq = hst[b].rhs_sq;
-            info[b].iterations = hst[b].iterations;
-            info[b].converged = hst[b].converged;
-            info[b].diverged = hst[b].diverged;
-            info[b].reserved = 0;
-        }
-    }
-    return PHIHIP_OK;
+    return cg_report(ctx, st[cur], v.batch, info, s);
 }
 
 // shift != nullptr: rhs is the UNBALANCED divergence and shift[b] its mean over the active cells (device doubles): the initial residual
@@ -1048,27 +1067,8 @@ static int cg_t(phihip_ctx* ctx, const GridView& v, const uint8_t* flags, int ma
         PHIHIP_TRY(place_workspace<T>(ctx, v, flags, mask_batch, (const T*)rhs, (T*)x, s));
     PHIHIP_TRY(ensure_buffer(ctx->ws_part, 5 * part_n * sizeof(double)));
     PHIHIP_TRY(ensure_buffer(ctx->ws_state, (size_t)4 * v.batch * sizeof(CgState)));
-    if (ctx->host_state_bytes < (size_t)2 * v.batch * sizeof(CgState)) {
-        if (ctx->host_state) (void)hipHostFree(ctx->host_state);
-        ctx->host_state = nullptr;
-        ctx->host_state_bytes = 0;
-        PHIHIP_CHECK_HIP(hipHostMalloc(&ctx->host_state, (size_t)2 * v.batch * sizeof(CgState), hipHostMallocDefault));
-        ctx->host_state_bytes = (size_t)2 * v.batch * sizeof(CgState);
-    }
-    if (!ctx->poll_ev[0]) {
-        PHIHIP_CHECK_HIP(hipEventCreate(&ctx->poll_ev[0]));
-        PHIHIP_CHECK_HIP(hipEventCreate(&ctx->poll_ev[1]));
-    }
-    if (ctx->host_flags_count < (size_t)v.batch) {
-        if (ctx->host_flags) (void)hipHostFree(ctx->host_flags);
-        ctx->host_flags = nullptr;
-        ctx->host_flags_count = 0;
-        PHIHIP_CHECK_HIP(hipHostMalloc((void**)&ctx->host_flags, (size_t)v.batch * sizeof(unsigned long long), hipHostMallocMapped));
-        memset(ctx->host_flags, 0, (size_t)v.batch * sizeof(unsigned long long));
-        PHIHIP_CHECK_HIP(hipHostGetDevicePointer((void**)&ctx->host_flags_dev, ctx->host_flags, 0));
-        ctx->host_flags_count = (size_t)v.batch;
-    }
-    const unsigned int seq = ++ctx->solve_seq;   // 0 never matches: flags of earlier solves read as "still running"
+    unsigned int seq;
+    PHIHIP_TRY(cg_host_prepare(ctx, v.batch, &seq));
     int checks = 0;
     T* r = (T*)ctx->ws_r.ptr;
     T* d[2] = {(T*)ctx->ws_d0.ptr, (T*)ctx->ws_d1.ptr};
@@ -1083,8 +1083,7 @@ static int cg_t(phihip_ctx* ctx, const GridView& v, const uint8_t* flags, int ma
     CgState* st[2] = {(CgState*)ctx->ws_state.ptr, (CgState*)ctx->ws_state.ptr + v.batch};
     int cur = 0;   // slot holding the most recent control block
     const bool has_flags = flags != nullptr;
-    CgParams prm;
-    prm.rtol = solve->rel_tol; prm.atol = solve->abs_tol; prm.max_iter = solve->max_iterations; prm.pad = 0;
+    const CgParams prm = cg_params(solve);
 
     MarchArgs<T> base;
     memset(&base, 0, sizeof(base));
@@ -1109,14 +1108,13 @@ static int cg_t(phihip_ctx* ctx, const GridView& v, const uint8_t* flags, int ma
     bool pending = false;
     int nblk_rr = g.nblk;   // workgroup count of the kernel that last wrote part_rr (RESID or UPDATE)
     const int axpy_blocks = (int)((v.cells + kBlock - 1) / kBlock < 2048 ? (v.cells + kBlock - 1) / kBlock : 2048);
-    CgState* hst = (CgState*)ctx->host_state;
     for (int k = 1; k <= solve->max_iterations; ++k) {
         T* d_old = d[(k - 1) & 1];
         T* d_new = d[k & 1];
         {
             MarchArgs<T> a = base;
             a.a = r; a.b = first ? r : d_old; a.o1 = d_new; a.part1 = part_dq; a.part2 = part_dr;
-            if (solve->check_every > 0) { a.host_flags = ctx->host_flags_dev; a.seq = seq; }
+            if (solve->check_every > 0) { a.host_flags = ctx->cg.host_flags_dev; a.seq = seq; }
             a.prologue = first ? PRO_FIRST : pro_beta;
             a.st_in = st[cur]; a.st_out = st[cur ^ 1]; a.pin1 = part_rr; a.pin2 = (first || !ad) ? part_yy : part_rq; a.nblk_in = nblk_rr;
             LaunchScope ls(ctx, PHIHIP_K_CG_MATVEC_DOT, s);
@@ -1166,24 +1164,9 @@ static int cg_t(phihip_ctx* ctx, const GridView& v, const uint8_t* flags, int ma
             cur ^= 1;
             nblk_rr = r_only ? g_ur.nblk : g_up.nblk;
         }
-        if (solve->check_every > 0 && k < solve->max_iterations) {
-            // Tolerance mode. Every MATVEC prologue publishes its continue decision into host-mapped memory (publish_flag), so the host
-            // looks before each enqueue -- no peek kernel, no copy -- and stops as soon as every entry reports "done" for THIS solve
-            // (sequence number). Flags only go 1 -> 0 and frozen entries make every kernel return at once, so the launches that
-            // were enqueued ahead are harmless; an event every `check_every` iterations bounds that run-ahead to two intervals.
-            bool any = false;
-            for (int b = 0; b < v.batch && !any; ++b) {
-                const unsigned long long f = *(volatile unsigned long long*)(ctx->host_flags + b);
-                any = (unsigned int)(f >> 32) != seq || (f & 1ull);
-            }
-            if (!any) break;
-            if (k % solve->check_every == 0) {
-                const int slot = checks & 1;
-                PHIHIP_CHECK_HIP(hipEventRecord(ctx->poll_ev[slot], s));
-                if (checks > 0) PHIHIP_CHECK_HIP(hipEventSynchronize(ctx->poll_ev[slot ^ 1]));
-                ++checks;
-            }
-        }
+        bool stop = false;
+        PHIHIP_TRY(cg_poll(ctx, solve, k, seq, v.batch, &checks, s, &stop));
+        if (stop) break;
     }
     {   // fold the last reduction into the control block (or build it when no iteration ran)
         LaunchScope ls(ctx, PHIHIP_K_CG_SCALAR, s);
@@ -1196,22 +1179,8 @@ static int cg_t(phihip_ctx* ctx, const GridView& v, const uint8_t* flags, int ma
         hipLaunchKernelGGL(cg_flush_x<T>, dim3(axpy_blocks, v.batch), dim3(kBlock), 0, s, (T*)x, (const T*)d[0], (const T*)d[1],
                            (const CgState*)st[cur], v.cells);
     }
-    ctx->last_state = st[cur];
-    ctx->last_state_batch = v.batch;
     PHIHIP_CHECK_HIP(hipGetLastError());
-    if (info) {
-        PHIHIP_CHECK_HIP(hipMemcpyAsync(hst, st[cur], (size_t)v.batch * sizeof(CgState), hipMemcpyDeviceToHost, s));
-        PHIHIP_CHECK_HIP(hipStreamSynchronize(s));
-        for (int b = 0; b < v.batch; ++b) {
-            info[b].residual_sq = hst[b].rsq;
-            info[b].rhs_sq = hst[b].rhs_sq;
-            info[b].iterations = hst[b].iterations;
-            info[b].converged = hst[b].converged;
-            info[b].diverged = hst[b].diverged;
-            info[b].reserved = 0;
-        }
-    }
-    return PHIHIP_OK;
+    return cg_report(ctx, st[cur], v.batch, info, s);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1254,7 +1223,7 @@ static MarchArgs<T> slab_args(const GridView& v, const uint8_t* flags, const phi
     MarchArgs<T> a;
     memset(&a, 0, sizeof(a));
     a.flags = flags;
-    if (solve) { a.prm.rtol = solve->rel_tol; a.prm.atol = solve->abs_tol; a.prm.max_iter = solve->max_iterations; }
+    if (solve) a.prm = cg_params(solve);
     set_operator(a, v);
     return a;
 }
@@ -1315,8 +1284,7 @@ static int slab_update_t(phihip_ctx* ctx, const GridView& v, const uint8_t* flag
                          hipStream_t s) {
     SlabSetup su;
     PHIHIP_TRY(slab_setup(ctx, v, mask_batch, flags != nullptr, FAM_UPDATE, &su));
-    CgParams prm;
-    prm.rtol = solve->rel_tol; prm.atol = solve->abs_tol; prm.max_iter = solve->max_iterations; prm.pad = 0;
+    const CgParams prm = cg_params(solve);
     if (x_only) {
         const int axpy_blocks = (int)((v.cells + kBlock - 1) / kBlock < 2048 ? (v.cells + kBlock - 1) / kBlock : 2048);
         LaunchScope ls(ctx, PHIHIP_K_OTHER, s);
@@ -1368,37 +1336,14 @@ int run_slab_finish(phihip_ctx* ctx, const GridView& v, int first, const double*
                     int peek, hipStream_t s) {
     PHIHIP_TRY(ensure_buffer(ctx->ws_state, (size_t)3 * v.batch * sizeof(CgState)));
     CgState* st[3] = {(CgState*)ctx->ws_state.ptr, (CgState*)ctx->ws_state.ptr + v.batch, (CgState*)ctx->ws_state.ptr + 2 * v.batch};
-    CgParams prm;
-    prm.rtol = solve->rel_tol; prm.atol = solve->abs_tol; prm.max_iter = solve->max_iterations; prm.pad = 0;
+    const CgParams prm = cg_params(solve);
     // peek: the decision the next MATVEC prologue will take, written to a third slot so that the chain does not advance
     const int dst = peek ? 2 : (ctx->slab_cur ^ 1);
     hipLaunchKernelGGL(cg_state_kernel, dim3(v.batch), dim3(kBlock), 0, s, (int)(first ? PRO_FIRST : PRO_BETA), (const CgState*)st[ctx->slab_cur],
                        st[dst], sums_in, sums_in + v.batch, 1, prm);
-    if (!peek) {
-        ctx->slab_cur ^= 1;
-        ctx->last_state = st[ctx->slab_cur];
-        ctx->last_state_batch = v.batch;
-    }
-    if (ctx->host_state_bytes < (size_t)v.batch * sizeof(CgState)) {
-        if (ctx->host_state) (void)hipHostFree(ctx->host_state);
-        ctx->host_state = nullptr;
-        ctx->host_state_bytes = 0;
-        PHIHIP_CHECK_HIP(hipHostMalloc(&ctx->host_state, (size_t)v.batch * sizeof(CgState), hipHostMallocDefault));
-        ctx->host_state_bytes = (size_t)v.batch * sizeof(CgState);
-    }
-    CgState* hst = (CgState*)ctx->host_state;
-    PHIHIP_CHECK_HIP(hipMemcpyAsync(hst, st[peek ? 2 : ctx->slab_cur], (size_t)v.batch * sizeof(CgState), hipMemcpyDeviceToHost, s));
-    PHIHIP_CHECK_HIP(hipStreamSynchronize(s));
-    if (info)
-        for (int b = 0; b < v.batch; ++b) {
-            info[b].residual_sq = hst[b].rsq;
-            info[b].rhs_sq = hst[b].rhs_sq;
-            info[b].iterations = hst[b].iterations;
-            info[b].converged = hst[b].converged;
-            info[b].diverged = hst[b].diverged;
-            info[b].reserved = hst[b].cont;   // 1: the entry would keep iterating (used by the host loop to stop early)
-        }
-    return PHIHIP_OK;
+    if (!peek) ctx->slab_cur ^= 1;
+    // reserved = 1: the entry would keep iterating (used by the host loop to stop early)
+    return cg_report(ctx, st[peek ? 2 : ctx->slab_cur], v.batch, info, s, CG_REPORT_SYNC | CG_REPORT_CONT | (peek ? CG_REPORT_PEEK : 0));
 }
 
 int run_cg(phihip_ctx* ctx, const GridView& v, const uint8_t* flags, int mask_batch, const void* rhs, void* x,

@@ -728,7 +728,7 @@ int run_cg_resident(phihip_ctx* ctx, const GridView& v, const uint8_t* flags, in
     PHIHIP_TRY(ensure_adv_host_public(ctx));
     A.abort_host = ctx->adv_host_dev + 15;
     A.st_out = (CgState*)st_out;
-    A.prm.rtol = solve->rel_tol; A.prm.atol = solve->abs_tol; A.prm.max_iter = solve->max_iterations; A.prm.pad = 0;
+    A.prm = cg_params(solve);
     A.refresh_every = solve->refresh_every;
     const size_t lds = resident_lds_bytes(vpt);
     const dim3 grid((unsigned)(G * v.batch)), block(kResBlock);

@@ -246,7 +246,7 @@ static int cg_small_t(phihip_ctx* ctx, const GridView& v, const uint8_t* flags, 
     a.x = (T*)x;
     a.flags = flags;
     a.st_out = st_out;
-    a.prm.rtol = solve->rel_tol; a.prm.atol = solve->abs_tol; a.prm.max_iter = solve->max_iterations; a.prm.pad = 0;
+    a.prm = cg_params(solve);
     a.refresh_every = solve->refresh_every;
     a.dim3 = v.rank == 3 ? 1 : 0;
     a.adaptive = solve->method == PHIHIP_METHOD_CG_ADAPTIVE ? 1 : 0;

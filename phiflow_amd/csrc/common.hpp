@@ -132,6 +132,21 @@ struct DeviceBuffer {
     size_t bytes = 0;
 };
 
+// Host-side resources every CG driver shares (cg.hip: cg_host_prepare / cg_poll / cg_report allocate and use them, cg_host_release frees them)
+struct CgHost {
+    const CgState* last_state = nullptr;   // device control blocks of the most recent solve (run_export_residuals / run_export_relative_residual)
+    int last_state_batch = 0;
+    CgState* host_state = nullptr;         // pinned readback buffer
+    size_t host_state_bytes = 0;
+    hipEvent_t poll_ev[2] = {nullptr, nullptr};   // throttle of the host's run-ahead in tolerance mode
+    // tolerance mode: the MATVEC prologue publishes (solve sequence number << 32 | continue flag) per batch entry straight into this
+    // pinned, device-mapped array; the host reads it before every enqueue -- no peek kernel, no copy, no stream drain
+    unsigned long long* host_flags = nullptr;
+    unsigned long long* host_flags_dev = nullptr;
+    size_t host_flags_count = 0;
+    unsigned int solve_seq = 0;
+};
+
 }  // namespace phihip
 
 struct phihip_ctx {
@@ -221,17 +236,7 @@ struct phihip_ctx {
     long long small_cg_cells = 0;   // experiment switch (phihip_set_small_grid_solver(ctx, n > 1)): cell limit instead of the built-in rule
     bool small_cg = true;         // grids that fit one CU's LDS are solved by the single-kernel CG (cg_small.hip)
     int slab_cur = 0;             // control-block slot of the running slab-decomposed solve
-    void* last_state = nullptr;   // device control blocks of the most recent solve
-    int last_state_batch = 0;
-    void* host_state = nullptr;   // pinned readback buffer
-    size_t host_state_bytes = 0;
-    hipEvent_t poll_ev[2] = {nullptr, nullptr};   // throttle of the host's run-ahead in tolerance mode (cg.hip)
-    // tolerance mode: the MATVEC prologue publishes (solve sequence number << 32 | continue flag) per batch entry straight into this
-    // pinned, device-mapped array; the host reads it before every enqueue -- no peek kernel, no copy, no stream drain
-    unsigned long long* host_flags = nullptr;
-    unsigned long long* host_flags_dev = nullptr;
-    size_t host_flags_count = 0;
-    unsigned int solve_seq = 0;
+    phihip::CgHost cg;            // host side of the CG drivers
     // profiling
     bool profiling = false;
     struct EventPair {
@@ -381,6 +386,22 @@ int run_diffuse_coef_implicit(phihip_ctx*, const GridView&, const void* u, const
                               void* out, hipStream_t);
 int run_laplace_apply(phihip_ctx*, const GridView&, const uint8_t* flags, int mask_batch, const void* p, void* out, hipStream_t);
 int run_laplace_apply_multi(phihip_ctx*, const GridView* lattices, int count, const void* const* in, void* const* out, hipStream_t);   // MODE_APPLY, no flags: lattices of one tile configuration share a launch
+// host scaffolding of the CG drivers (cg.hip; diffuse_coef.hpp reaches it from project.hip's translation unit)
+CgParams cg_params(const phihip_solve*);
+// grows the pinned readback buffer and the host-mapped flag array to `batch` entries, creates the poll events (allocates nothing once the sizes
+// suffice: a captured solve after a warm-up) and numbers the solve
+int cg_host_prepare(phihip_ctx*, int batch, unsigned int* seq);
+void cg_host_release(phihip_ctx*);
+// tolerance mode, after the launches of iteration k: *stop = every entry reports "done" for solve `seq`; bounds the host's run-ahead
+int cg_poll(phihip_ctx*, const phihip_solve*, int k, unsigned int seq, int batch, int* checks, hipStream_t, bool* stop);
+enum CgReportFlags {
+    CG_REPORT_PEEK = 1,   // `state` is a look ahead: the context's record of the most recent solve stays
+    CG_REPORT_SYNC = 2,   // copy and synchronise without `info` too
+    CG_REPORT_CONT = 4    // info.reserved = the entry's continue flag (host loop of the slab-decomposed solve)
+};
+// records `state` as the most recent solve's control blocks; with `info`: copies them to the host, synchronises the stream and fills info[0..batch).
+// `aborted` != NULL (resident solver): set when an entry carries iterations < 0 -- no entry is reported then
+int cg_report(phihip_ctx*, const CgState* state, int batch, phihip_solve_info* info, hipStream_t, int flags = 0, bool* aborted = nullptr);
 int run_export_residuals(phihip_ctx*, int batch, double* out, hipStream_t);
 int run_export_relative_residual(phihip_ctx*, int batch, double* out, hipStream_t);
 int run_cg(phihip_ctx*, const GridView&, const uint8_t* flags, int mask_batch, const void* rhs, void* x, const phihip_solve*, phihip_solve_info*, hipStream_t);

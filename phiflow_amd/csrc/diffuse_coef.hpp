@@ -325,27 +325,8 @@ static int coef_cg_t(phihip_ctx* ctx, const CoefOp& op0, int batch, const T* coe
     PHIHIP_TRY(ensure_buffer(ctx->ws_coef_d1, vec_bytes));
     PHIHIP_TRY(ensure_buffer(ctx->ws_coef_part, 5 * part_n * sizeof(double)));
     PHIHIP_TRY(ensure_buffer(ctx->ws_coef_state, (size_t)2 * batch * sizeof(CgState)));
-    if (ctx->host_state_bytes < (size_t)2 * batch * sizeof(CgState)) {
-        if (ctx->host_state) (void)hipHostFree(ctx->host_state);
-        ctx->host_state = nullptr;
-        ctx->host_state_bytes = 0;
-        PHIHIP_CHECK_HIP(hipHostMalloc(&ctx->host_state, (size_t)2 * batch * sizeof(CgState), hipHostMallocDefault));
-        ctx->host_state_bytes = (size_t)2 * batch * sizeof(CgState);
-    }
-    if (!ctx->poll_ev[0]) {
-        PHIHIP_CHECK_HIP(hipEventCreate(&ctx->poll_ev[0]));
-        PHIHIP_CHECK_HIP(hipEventCreate(&ctx->poll_ev[1]));
-    }
-    if (ctx->host_flags_count < (size_t)batch) {
-        if (ctx->host_flags) (void)hipHostFree(ctx->host_flags);
-        ctx->host_flags = nullptr;
-        ctx->host_flags_count = 0;
-        PHIHIP_CHECK_HIP(hipHostMalloc((void**)&ctx->host_flags, (size_t)batch * sizeof(unsigned long long), hipHostMallocMapped));
-        memset(ctx->host_flags, 0, (size_t)batch * sizeof(unsigned long long));
-        PHIHIP_CHECK_HIP(hipHostGetDevicePointer((void**)&ctx->host_flags_dev, ctx->host_flags, 0));
-        ctx->host_flags_count = (size_t)batch;
-    }
-    const unsigned int seq = ++ctx->solve_seq;
+    unsigned int seq;
+    PHIHIP_TRY(cg_host_prepare(ctx, batch, &seq));
     int checks = 0;
     T* r = (T*)ctx->ws_coef_r.ptr;
     T* d[2] = {(T*)ctx->ws_coef_d0.ptr, (T*)ctx->ws_coef_d1.ptr};
@@ -358,8 +339,7 @@ static int coef_cg_t(phihip_ctx* ctx, const CoefOp& op0, int batch, const T* coe
     const int pro_alpha = ad ? PRO_ALPHA_AD : PRO_ALPHA, pro_beta = ad ? PRO_BETA_AD : PRO_BETA;
     CgState* st[2] = {(CgState*)ctx->ws_coef_state.ptr, (CgState*)ctx->ws_coef_state.ptr + batch};
     int cur = 0;
-    CgParams prm;
-    prm.rtol = solve->rel_tol; prm.atol = solve->abs_tol; prm.max_iter = solve->max_iterations; prm.pad = 0;
+    const CgParams prm = cg_params(solve);
     CoefArgs<T> base;
     memset(&base, 0, sizeof(base));
     base.coef = coef;
@@ -372,14 +352,13 @@ static int coef_cg_t(phihip_ctx* ctx, const CoefOp& op0, int batch, const T* coe
         PHIHIP_TRY((coef_launch<T, CM_RESID>(op, batch, a, s)));
     }
     bool first = true;
-    CgState* hst = (CgState*)ctx->host_state;
     for (int k = 1; k <= solve->max_iterations; ++k) {
         T* d_old = d[(k - 1) & 1];
         T* d_new = d[k & 1];
         {   // d_new = r + beta d_old (the first one reads r in place of d_old with beta = 0)
             CoefArgs<T> a = base;
             a.a = r; a.b = first ? r : d_old; a.o1 = d_new; a.part1 = part_dq; a.part2 = ad ? part_dr : nullptr;
-            if (solve->check_every > 0) { a.host_flags = ctx->host_flags_dev; a.seq = seq; }
+            if (solve->check_every > 0) { a.host_flags = ctx->cg.host_flags_dev; a.seq = seq; }
             a.prologue = first ? PRO_FIRST : pro_beta;
             a.st_in = st[cur]; a.st_out = st[cur ^ 1]; a.pin1 = part_rr; a.pin2 = (first || !ad) ? part_yy : part_rq;
             LaunchScope ls(ctx, PHIHIP_K_CG_MATVEC_DOT, s);
@@ -422,20 +401,9 @@ static int coef_cg_t(phihip_ctx* ctx, const CoefOp& op0, int batch, const T* coe
             PHIHIP_TRY((coef_launch<T, CM_UPDATE>(op, batch, a, s)));
             cur ^= 1;
         }
-        if (solve->check_every > 0 && k < solve->max_iterations) {   // tolerance mode: as cg.hip cg_t
-            bool any = false;
-            for (int bi = 0; bi < batch && !any; ++bi) {
-                const unsigned long long f = *(volatile unsigned long long*)(ctx->host_flags + bi);
-                any = (unsigned int)(f >> 32) != seq || (f & 1ull);
-            }
-            if (!any) break;
-            if (k % solve->check_every == 0) {
-                const int slot = checks & 1;
-                PHIHIP_CHECK_HIP(hipEventRecord(ctx->poll_ev[slot], s));
-                if (checks > 0) PHIHIP_CHECK_HIP(hipEventSynchronize(ctx->poll_ev[slot ^ 1]));
-                ++checks;
-            }
-        }
+        bool stop = false;
+        PHIHIP_TRY(cg_poll(ctx, solve, k, seq, batch, &checks, s, &stop));
+        if (stop) break;
     }
     {
         LaunchScope ls(ctx, PHIHIP_K_CG_SCALAR, s);
@@ -443,22 +411,8 @@ static int coef_cg_t(phihip_ctx* ctx, const CoefOp& op0, int batch, const T* coe
                            st[cur ^ 1], (const double*)part_rr, (const double*)((first || !ad) ? part_yy : part_rq), op.nblk, prm);
         cur ^= 1;
     }
-    ctx->last_state = st[cur];
-    ctx->last_state_batch = batch;
     PHIHIP_CHECK_HIP(hipGetLastError());
-    if (info) {
-        PHIHIP_CHECK_HIP(hipMemcpyAsync(hst, st[cur], (size_t)batch * sizeof(CgState), hipMemcpyDeviceToHost, s));
-        PHIHIP_CHECK_HIP(hipStreamSynchronize(s));
-        for (int bi = 0; bi < batch; ++bi) {
-            info[bi].residual_sq = hst[bi].rsq;
-            info[bi].rhs_sq = hst[bi].rhs_sq;
-            info[bi].iterations = hst[bi].iterations;
-            info[bi].converged = hst[bi].converged;
-            info[bi].diverged = hst[bi].diverged;
-            info[bi].reserved = 0;
-        }
-    }
-    return PHIHIP_OK;
+    return cg_report(ctx, st[cur], batch, info, s);
 }
 
 // diffuse.implicit: solve_linear(sharpen, y = field, x0 = field) with sharpen(x) = explicit(x, a, -dt) = x + L_a x (w_d = -kdt_d / dx_d^2).
