@@ -20,6 +20,7 @@ def main():
     ap.add_argument("--size", type=int, default=128)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--jit", action="store_true")
+    ap.add_argument("--preconditioner", default=None, choices=["multigrid"], help="CG preconditioned by a multigrid V-cycle (fewer iterations on large grids)")
     args = ap.parse_args()
     n = args.size
     domain = Box(x=100, y=100)
@@ -33,7 +34,8 @@ def main():
         smoke = advect.mac_cormack(smoke, velocity, dt) + inflow
         buoyancy = resample(smoke * (0, 0.1), to=velocity)
         velocity = advect.semi_lagrangian(velocity, velocity, dt) + buoyancy * dt
-        velocity, pressure = fluid.make_incompressible(velocity, (), Solve('CG', 1e-3, x0=pressure, max_iterations=200 if args.jit else 1000))
+        velocity, pressure = fluid.make_incompressible(velocity, (), Solve('CG', 1e-3, x0=pressure, max_iterations=200 if args.jit else 1000,
+                                                                             preconditioner=args.preconditioner))
         return velocity, smoke, pressure
     if args.jit:
         step = jit_compile(step)

@@ -21,6 +21,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=128)
     ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--preconditioner", default=None, choices=["multigrid"], help="CG preconditioned by a multigrid V-cycle (fewer iterations on large grids)")
     ap.add_argument("--fp64", action="store_true", help="double precision with Solve('CG', 1e-10) like the reference notebook (1e-12 there)")
     args = ap.parse_args()
     with precision(64 if args.fp64 else 32):
@@ -46,7 +47,7 @@ def run(args):
     for _ in range(args.steps):
         v = advect.semi_lagrangian(v, v, dt)
         # (fp32 CG on a periodic 128^3+ box stagnates near a relative residual of 1e-4: condition number x machine epsilon)
-        v, p = fluid.make_incompressible(v, (), Solve('CG', 1e-10 if args.fp64 else 1e-3, x0=p))
+        v, p = fluid.make_incompressible(v, (), Solve('CG', 1e-10 if args.fp64 else 1e-3, x0=p, preconditioner=args.preconditioner))
     e1 = energy(v)
     wall = time.perf_counter() - t0
     print(f"{args.steps} steps of {n}^3: {wall / args.steps * 1e3:.2f} ms per step, kinetic energy {e0:.4f} -> {e1:.4f}, "

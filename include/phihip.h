@@ -67,7 +67,13 @@ typedef struct phihip_grid {
 
 typedef enum phihip_method {
     PHIHIP_METHOD_CG = 0,           /* Solve('CG', ...): alpha = r.r / d.Ad, beta = r'.r' / r.r */
-    PHIHIP_METHOD_CG_ADAPTIVE = 1   /* Solve('CG-adaptive', ...) (examples/grids/Fluid_Logo.ipynb): alpha = d.r / d.Ad, d' = r' - (r'.Ad / d.Ad) d */
+    PHIHIP_METHOD_CG_ADAPTIVE = 1,  /* Solve('CG-adaptive', ...) (examples/grids/Fluid_Logo.ipynb): alpha = d.r / d.Ad, d' = r' - (r'.Ad / d.Ad) d */
+    PHIHIP_METHOD_CG_MULTIGRID = 2  /* Solve('CG', ..., preconditioner='multigrid'): 'CG' preconditioned by one geometric multigrid V-cycle per iteration
+                                     * (z = M r, alpha = r.z / d.Ad, beta = r'.z' / r.z). Same stopping rule on the PLAIN residual, same refresh, polling and
+                                     * reporting as 'CG'; `iterations` counts preconditioned iterations. Pressure solves only (phihip_cg_solve,
+                                     * phihip_make_incompressible and its backward pass): the diffuse_implicit, shifted and slab entry points return
+                                     * PHIHIP_ERR_UNSUPPORTED. On a singular operator (no OPEN side) the returned pressure may differ from plain CG's by a
+                                     * constant per connected fluid region -- the mean is left alone -- the projected velocity does not. */
 } phihip_method;
 
 /* phiml.math.Solve subset used by fluid.make_incompressible (phi/physics/fluid.py:96,145-156) */
@@ -78,7 +84,7 @@ typedef struct phihip_solve {
     int32_t refresh_every;    /* recompute r = y - A x every n-th iteration (PhiML: 50); 0 = never */
     int32_t check_every;      /* > 0: tolerance mode -- the host watches the continue flags the kernels publish into mapped host memory
                                * and throttles its run-ahead with an event every n iterations; 0 = run max_iterations launches */
-    int32_t method;           /* phihip_method: 0 = 'CG' (also what 'auto' maps to), 1 = 'CG-adaptive' */
+    int32_t method;           /* phihip_method: 0 = 'CG' (also what 'auto' maps to), 1 = 'CG-adaptive', 2 = 'CG' with the multigrid preconditioner */
 } phihip_solve;
 
 /* per batch entry result of the linear solve (phiml SolveInfo: iterations, residual, converged, diverged) */
@@ -228,6 +234,18 @@ int phihip_laplace_apply(phihip_ctx* ctx, const phihip_grid* grid, const uint8_t
 /* x holds x0 on entry and the solution on exit. info: array of grid->batch entries or NULL (no host sync). */
 int phihip_cg_solve(phihip_ctx* ctx, const phihip_grid* grid, const uint8_t* flags, int mask_batch, const void* rhs,
                     void* x, const phihip_solve* solve, phihip_solve_info* info, void* stream);
+/* One multigrid V-cycle on its own: z = M r, the preconditioner of PHIHIP_METHOD_CG_MULTIGRID for the operator A of phihip_cg_solve on this grid /
+ * these flags -- a fixed, symmetric linear operator M ~ A^-1. A is NEGATIVE semidefinite on the active cells and the identity on inactive ones, and M
+ * has the same signs: <u, M u> < 0 for u supported on active cells, z = r on inactive cells. Levels: cells per axis n -> ceil(n / 2) until the smallest
+ * axis has <= 4 cells, Galerkin coarse operators of piecewise-constant prolongation, prolongation x 2, damped Jacobi (0.8) 2 + 2 sweeps, 60 sweeps on
+ * the coarsest level. r and z: [batch][res...], must not alias. The hierarchy is rebuilt from the flags by every call. */
+int phihip_precondition_apply(phihip_ctx* ctx, const phihip_grid* grid, const uint8_t* flags, int mask_batch, const void* r, void* z, void* stream);
+/* Parameters of the V-cycle (a value <= 0 keeps the current one): Jacobi sweeps before and after the coarse correction (one number: equal counts keep the
+ * cycle symmetric; default 2), the axis length at which coarsening stops (4), sweeps of each half of the coarsest-level solve (30), damping (0.8).
+ * The defaults need no call. */
+int phihip_set_multigrid(phihip_ctx* ctx, int sweeps, int coarsest_cells, int coarsest_sweeps, double omega);
+/* out = {levels, kernel launches} of the most recent V-cycle on this context ({0, 0}: none yet) */
+int phihip_query_multigrid(phihip_ctx* ctx, int32_t out[2]);
 /* The same CG on  (identity * I + scale * L) x = rhs,  L = the operator of phihip_cg_solve on this grid without obstacle flags
  * (neighbour rule from the codes: PERIODIC wraps, CLOSED = no flux / zero-gradient, OPEN = zero ghost). identity = 1, scale = -k dt is
  * the system of implicit diffusion; this entry is what the PhiML plug-in uses when `solve_linear` hands it such a matrix. The system

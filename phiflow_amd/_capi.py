@@ -33,6 +33,7 @@ EXPORTED_SYMBOLS = (
     "phihip_grid_sample", "phihip_grid_sample_backward", "phihip_set_deferred_x_update", "phihip_set_advect_halo", "phihip_advect_fallback_stats", "phihip_set_advect_chunk", "phihip_set_advect_windows_2d", "phihip_query_advect_chunk", "phihip_set_autotune", "phihip_allreduce_residual", "phihip_set_single_reduction_cg", "phihip_set_resident_cg", "phihip_set_advect_dma", "phihip_workspace_placement",
     "phihip_diffuse_explicit_centered_coef", "phihip_diffuse_implicit_centered_coef",
     "phihip_advect_centered_vector", "phihip_staggered_to_centered", "phihip_centered_vector_to_staggered",
+    "phihip_precondition_apply", "phihip_set_multigrid", "phihip_query_multigrid",
 )
 
 
@@ -247,6 +248,9 @@ class Library:
         d.phihip_centered_vector_to_staggered.argtypes = [c_void_p, POINTER(Grid), c_void_p, c_int, POINTER((c_int32 * 2) * 3),
                                                           POINTER((c_double * 2) * 3), POINTER(_Ptr3), c_void_p]
         d.phihip_query_plan.argtypes = [c_void_p, POINTER(Grid), c_int, c_int, POINTER(c_int32 * 6)]
+        d.phihip_precondition_apply.argtypes = [c_void_p, POINTER(Grid), c_void_p, c_int, c_void_p, c_void_p, c_void_p]
+        d.phihip_set_multigrid.argtypes = [c_void_p, c_int, c_int, c_int, c_double]
+        d.phihip_query_multigrid.argtypes = [c_void_p, POINTER(c_int32 * 2)]
         for name in EXPORTED_SYMBOLS:
             if name not in ("phihip_version", "phihip_last_error", "phihip_build_id"):
                 getattr(d, name).restype = c_int
@@ -466,6 +470,20 @@ class Context:
         self.lib.check(self.lib.dll.phihip_cg_solve(self.handle, ctypes.byref(grid), flags or None, int(mask_batch), rhs, x,
                                                     ctypes.byref(solve), info, stream or None))
         return list(info) if want_info else None
+
+    def precondition_apply(self, grid, flags, mask_batch, r, z, stream=0):
+        """ one multigrid V-cycle z = M r (M ~ A^-1, the preconditioner of METHOD_CG_MULTIGRID); r and z must not alias """
+        self.lib.check(self.lib.dll.phihip_precondition_apply(self.handle, ctypes.byref(grid), flags or None, int(mask_batch), r, z, stream or None))
+
+    def set_multigrid(self, sweeps: int = 0, coarsest_cells: int = 0, coarsest_sweeps: int = 0, omega: float = 0.0):
+        """ parameters of the V-cycle; a value <= 0 keeps the current one (defaults 2, 4, 30, 0.8) """
+        self.lib.check(self.lib.dll.phihip_set_multigrid(self.handle, int(sweeps), int(coarsest_cells), int(coarsest_sweeps), float(omega)))
+
+    def query_multigrid(self) -> dict:
+        """ levels and kernel launches of the most recent V-cycle on this context """
+        out = (c_int32 * 2)()
+        self.lib.check(self.lib.dll.phihip_query_multigrid(self.handle, ctypes.byref(out)))
+        return {"levels": int(out[0]), "launches": int(out[1])}
 
     def cg_solve_shifted(self, grid, identity, scale, rhs, x, solve: Solve, want_info=True, stream=0):
         """ CG on (identity * I + scale * L) x = rhs with the pressure operator L of `grid` (no obstacle flags) """

@@ -356,7 +356,8 @@ int phihip_ctx_create(int device, phihip_ctx** out) {
 static DeviceBuffer phihip_ctx::* const kCtxBuffers[] = {
     &phihip_ctx::ws_r, &phihip_ctx::ws_d0, &phihip_ctx::ws_d1, &phihip_ctx::ws_div, &phihip_ctx::ws_part, &phihip_ctx::ws_state, &phihip_ctx::ws_scalars, &phihip_ctx::ws_rhs,
     &phihip_ctx::ws_adv, &phihip_ctx::ws_adv_flags, &phihip_ctx::ws_adj_q, &phihip_ctx::ws_adj_l, &phihip_ctx::ws_cg1, &phihip_ctx::ws_adj_g, &phihip_ctx::ws_res, &phihip_ctx::ws_adv_const,
-    &phihip_ctx::ws_coef_r, &phihip_ctx::ws_coef_d0, &phihip_ctx::ws_coef_d1, &phihip_ctx::ws_coef_part, &phihip_ctx::ws_coef_state, &phihip_ctx::ws_coef_rhs};
+    &phihip_ctx::ws_coef_r, &phihip_ctx::ws_coef_d0, &phihip_ctx::ws_coef_d1, &phihip_ctx::ws_coef_part, &phihip_ctx::ws_coef_state, &phihip_ctx::ws_coef_rhs,
+    &phihip_ctx::ws_mg_r, &phihip_ctx::ws_mg_d0, &phihip_ctx::ws_mg_d1, &phihip_ctx::ws_mg_z, &phihip_ctx::ws_mg_t, &phihip_ctx::ws_mg_levels, &phihip_ctx::ws_mg_part, &phihip_ctx::ws_mg_state};
 
 int phihip_ctx_destroy(phihip_ctx* ctx) {
     if (!ctx) return PHIHIP_OK;
@@ -677,7 +678,8 @@ static int check_solve(const phihip_solve* solve) {
     PHIHIP_REQUIRE(solve->max_iterations >= 0, "solve.max_iterations must be >= 0");
     PHIHIP_REQUIRE(solve->rel_tol >= 0 && solve->abs_tol >= 0, "solve tolerances must be >= 0");
     PHIHIP_REQUIRE(solve->refresh_every >= 0 && solve->check_every >= 0, "solve.refresh_every / check_every must be >= 0");
-    PHIHIP_REQUIRE(solve->method == PHIHIP_METHOD_CG || solve->method == PHIHIP_METHOD_CG_ADAPTIVE, "solve.method must be a phihip_method");
+    PHIHIP_REQUIRE(solve->method == PHIHIP_METHOD_CG || solve->method == PHIHIP_METHOD_CG_ADAPTIVE || solve->method == PHIHIP_METHOD_CG_MULTIGRID,
+                   "solve.method must be a phihip_method");
     return PHIHIP_OK;
 }
 
@@ -699,6 +701,30 @@ int phihip_cg_solve(phihip_ctx* ctx, const phihip_grid* grid, const uint8_t* fla
     PHIHIP_TRY(check_solve(solve));
     note_align(v, rhs); note_align(v, x); note_align(v, flags, 3u);
     return run_cg(ctx, v, flags, mask_batch, rhs, x, solve, info, s);
+}
+
+int phihip_precondition_apply(phihip_ctx* ctx, const phihip_grid* grid, const uint8_t* flags, int mask_batch, const void* r, void* z, void* stream) {
+    PHIHIP_ENTER(ctx, grid);
+    PHIHIP_REQUIRE(r && z && r != z, "precondition_apply: r / z NULL or aliased");
+    PHIHIP_REQUIRE(mask_batch == 1 || mask_batch == v.batch, "mask_batch must be 1 or grid.batch");
+    return run_multigrid_apply(ctx, v, flags, mask_batch, r, z, s);
+}
+
+int phihip_set_multigrid(phihip_ctx* ctx, int sweeps, int coarsest_cells, int coarsest_sweeps, double omega) {
+    PHIHIP_REQUIRE(ctx != nullptr, "ctx is NULL");
+    PHIHIP_REQUIRE(sweeps <= 16 && coarsest_cells <= 1024 && coarsest_sweeps <= 1000 && omega < 1.0, "set_multigrid: sweeps <= 16, coarsest_cells <= 1024, coarsest_sweeps <= 1000, omega < 1");
+    if (sweeps > 0) ctx->mg_sweeps = sweeps;
+    if (coarsest_cells > 0) ctx->mg_coarsest = coarsest_cells;
+    if (coarsest_sweeps > 0) ctx->mg_bottom = coarsest_sweeps;
+    if (omega > 0) ctx->mg_omega = omega;
+    return PHIHIP_OK;
+}
+
+int phihip_query_multigrid(phihip_ctx* ctx, int32_t out[2]) {
+    PHIHIP_REQUIRE(ctx != nullptr && out != nullptr, "ctx / out is NULL");
+    out[0] = ctx->mg_last_levels;
+    out[1] = ctx->mg_last_launches;
+    return PHIHIP_OK;
 }
 
 int phihip_cg_solve_shifted(phihip_ctx* ctx, const phihip_grid* grid, double identity, double scale, const void* rhs, void* x,
@@ -872,7 +898,7 @@ int phihip_make_incompressible(phihip_ctx* ctx, const phihip_grid* grid, void* c
     const void* cu[3] = {u[0], u[1], u[2]};
     const int guard = balance & PHIHIP_DIV_FINITE_GUARD;
     balance = (balance & ~PHIHIP_DIV_FINITE_GUARD) ? PHIHIP_DIV_BALANCE : 0;
-    if (balance && cg_uses_marching(ctx, v) && !v.unaligned) {
+    if (balance && cg_uses_marching(ctx, v) && !v.unaligned && solve->method != PHIHIP_METHOD_CG_MULTIGRID) {
         // divergence + partial sums in one pass; the mean is subtracted inside the solver's initial residual (no extra pass over div)
         PHIHIP_TRY(run_divergence(ctx, v, cu, flags, mask_batch, 2 | guard, div, s));
         PHIHIP_TRY(run_cg_balancing(ctx, v, flags, mask_batch, div, pressure, solve, info, (const double*)ctx->ws_scalars.ptr, s));

@@ -1348,6 +1348,8 @@ int run_slab_finish(phihip_ctx* ctx, const GridView& v, int first, const double*
 
 int run_cg(phihip_ctx* ctx, const GridView& v, const uint8_t* flags, int mask_batch, const void* rhs, void* x,
            const phihip_solve* solve, phihip_solve_info* info, hipStream_t s) {
+    // the one place that dispatches on the preconditioner: the single-kernel, resident and single-reduction solvers are not taken with it
+    if (solve->method == PHIHIP_METHOD_CG_MULTIGRID) return run_cg_multigrid(ctx, v, flags, mask_batch, rhs, x, solve, info, s);
     return v.dtype == PHIHIP_F64 ? cg_t<double>(ctx, v, flags, mask_batch, rhs, x, solve, info, nullptr, s)
                                  : cg_t<float>(ctx, v, flags, mask_batch, rhs, x, solve, info, nullptr, s);
 }
@@ -1356,8 +1358,11 @@ bool cg_uses_marching(const phihip_ctx* ctx, const GridView& v) { return v.op_cu
 
 int run_cg_balancing(phihip_ctx* ctx, const GridView& v, const uint8_t* flags, int mask_batch, void* rhs, void* x, const phihip_solve* solve,
                      phihip_solve_info* info, const double* shift, hipStream_t s) {
+    if (solve->method == PHIHIP_METHOD_CG_MULTIGRID) { set_error("cg: the preconditioned solver takes a balanced right-hand side"); return PHIHIP_ERR_BAD_ARG; }
     return v.dtype == PHIHIP_F64 ? cg_t<double>(ctx, v, flags, mask_batch, rhs, x, solve, info, shift, s)
                                  : cg_t<float>(ctx, v, flags, mask_batch, rhs, x, solve, info, shift, s);
 }
 
 }  // namespace phihip
+
+#include "multigrid.hpp"

@@ -157,6 +157,14 @@ struct phihip_ctx {
     phihip::DeviceBuffer ws_r, ws_d0, ws_d1, ws_div, ws_part, ws_state, ws_scalars, ws_rhs, ws_adv, ws_adv_flags, ws_adj_q, ws_adj_l, ws_cg1, ws_adj_g, ws_res, ws_adv_const;
     // diffusion with a varying / per-axis diffusivity (diffuse_coef.hpp): its own CG vectors, partial sums, control blocks and right-hand side
     phihip::DeviceBuffer ws_coef_r, ws_coef_d0, ws_coef_d1, ws_coef_part, ws_coef_state, ws_coef_rhs;
+    // multigrid-preconditioned CG (multigrid.hpp): CG vectors, the preconditioned residual z, a smoothing temporary, every coarse level (x, b,
+    // temporary, diagonal and couplings) in one buffer, partial sums and control blocks. Not subject to place_workspace.
+    phihip::DeviceBuffer ws_mg_r, ws_mg_d0, ws_mg_d1, ws_mg_z, ws_mg_t, ws_mg_levels, ws_mg_part, ws_mg_state;
+    int mg_sweeps = 2;            // Jacobi sweeps before and after the coarse correction (equal: the cycle stays symmetric)
+    int mg_bottom = 30;           // the coarsest level runs 2 * mg_bottom sweeps
+    int mg_coarsest = 4;          // coarsen until the smallest axis has at most this many cells
+    double mg_omega = 0.8;
+    int mg_last_levels = 0, mg_last_launches = 0;   // of the most recent V-cycle (phihip_query_multigrid)
     int adv_last_nblk = 0;        // (tile, plane) units of the most recent LDS-staged advection launch (capacity of its fix-up work list)
     bool adv_ctl_clear = false;   // the work list's control block in ws_adv_flags has been zeroed
     // Adaptive reach (r4). Each LDS-staged pass publishes how many (tile, plane) units fell back to the gather path (the fix-up launch writes
@@ -407,6 +415,9 @@ int run_export_relative_residual(phihip_ctx*, int batch, double* out, hipStream_
 int run_cg(phihip_ctx*, const GridView&, const uint8_t* flags, int mask_batch, const void* rhs, void* x, const phihip_solve*, phihip_solve_info*, hipStream_t);
 // projection: rhs = unbalanced divergence, shift[b] = its mean over the active cells (run_divergence with balance = 2); balanced in place
 bool cg_uses_marching(const phihip_ctx*, const GridView&);
+// multigrid.hpp (compiled through cg.hip): z = M r, one V-cycle; CG preconditioned by it (PHIHIP_METHOD_CG_MULTIGRID, dispatched by run_cg)
+int run_multigrid_apply(phihip_ctx*, const GridView&, const uint8_t* flags, int mask_batch, const void* r, void* z, hipStream_t);
+int run_cg_multigrid(phihip_ctx*, const GridView&, const uint8_t* flags, int mask_batch, const void* rhs, void* x, const phihip_solve*, phihip_solve_info*, hipStream_t);
 int run_cg_balancing(phihip_ctx*, const GridView&, const uint8_t* flags, int mask_batch, void* rhs, void* x, const phihip_solve*, phihip_solve_info*,
                      const double* shift, hipStream_t);
 

@@ -447,6 +447,7 @@ int run_diffuse_coef_implicit(phihip_ctx* ctx, const GridView& v, const void* u,
                               int c_batch, const int32_t c_bc[3][2], const double c_val[3][2], const double kdt[3], const phihip_solve* solve,
                               phihip_solve_info* info, void* out, hipStream_t s) {
     if (v.cells >= (1LL << 31)) { set_error("diffuse_implicit: more than 2^31 cells per batch entry are not supported"); return PHIHIP_ERR_UNSUPPORTED; }
+    if (solve->method == PHIHIP_METHOD_CG_MULTIGRID) { set_error("diffuse_implicit: the multigrid preconditioner covers the pressure solve only"); return PHIHIP_ERR_UNSUPPORTED; }
     const ScalarBc ub = make_scalar_bc(v, s_bc, s_val), cb = make_scalar_bc(v, c_bc, c_val);
     if (v.dtype == PHIHIP_F64) return diffuse_coef_implicit_t<double>(ctx, v, u, ub, coef, c_batch, cb, kdt, solve, info, out, s);
     return diffuse_coef_implicit_t<float>(ctx, v, u, ub, coef, c_batch, cb, kdt, solve, info, out, s);

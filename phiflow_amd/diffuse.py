@@ -197,6 +197,8 @@ def implicit(field: Field, diffusivity, dt: float, solve=None, order: int = 2) -
     if order != 2:
         raise NotImplementedError("HIP backend: diffuse.implicit implements order=2 only")
     solve = Solve('CG') if solve is None else solve
+    if solve.preconditioner is not None or (solve.gradient_solve is not None and solve.gradient_solve.preconditioner is not None):
+        raise NotImplementedError("HIP backend: diffuse.implicit takes no preconditioner (Solve(preconditioner='multigrid') covers the pressure solve only)")
     if solve.x0 is not None:
         raise NotImplementedError("HIP backend: diffuse.implicit starts from x0 = field (the reference's default); pass solve.x0=None")
     vals = field.values if field.is_staggered else [field.values]

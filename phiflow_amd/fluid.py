@@ -218,6 +218,7 @@ def make_incompressible(velocity: Field,
         raise NotImplementedError("HIP backend: make_incompressible implements the StaggeredGrid path (wide_stencil=False) only")
     if solve.method not in Solve.METHODS:
         raise NotImplementedError(f"HIP backend: Solve(method={solve.method!r}) is not available, use one of {tuple(Solve.METHODS)}")
+    solve.c_method()     # (an unknown preconditioner, or one with 'CG-adaptive', is refused before anything is computed)
     obstacles = _get_obstacles_for(obstacles, velocity)
     be = velocity.backend
     OB = _obstacle_batch(obstacles)

@@ -135,9 +135,11 @@ class SlabSolver:
 
     # --- the solve ---
     def solve(self, rhs: torch.Tensor, x: torch.Tensor, rel_tol=1e-5, abs_tol=0.0, max_iterations=1000, refresh_every=50, check_every=10,
-              flags: Optional[torch.Tensor] = None):
+              flags: Optional[torch.Tensor] = None, preconditioner: Optional[str] = None):
         """ rhs, x: this rank's slabs (batch, planes, y, z); x holds x0 on entry and the solution on exit. Returns the list of
-        `SolveInfo` (identical on every rank). """
+        `SolveInfo` (identical on every rank). The slab-decomposed solve is plain CG: a preconditioner is refused. """
+        if preconditioner is not None:
+            raise NotImplementedError(f"HIP backend: the slab-decomposed solve takes no preconditioner (got {preconditioner!r})")
         ctx, g, halo, s = self.be.ctx, self.grid, self.halo, self.be.stream()
         csolve = _capi.Solve(float(rel_tol), float(abs_tol), int(max_iterations), int(refresh_every), int(check_every), 0)
         fl = flags.data_ptr() if flags is not None else 0

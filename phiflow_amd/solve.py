@@ -37,7 +37,7 @@ class SolveInfo:
 
 @dataclass(frozen=True)
 class Solve:
-    """ `Solve(method, rel_tol, abs_tol, x0, max_iterations, suppress, preprocess_y, rank_deficiency)`.
+    """ `Solve(method, rel_tol, abs_tol, x0, max_iterations, suppress, preprocess_y, rank_deficiency, ..., preconditioner=None)`.
     Unset tolerances default to 1e-5 (fp32) / 1e-12 (fp64). Supported methods: 'CG', 'auto' (-> CG) and 'CG-adaptive'
     (examples/grids/Fluid_Logo.ipynb; SURVEY Appendix B.2: alpha = d.r / d.Ad, d' = r' - (r'.Ad / d.Ad) d). """
     method: str = 'auto'
@@ -54,6 +54,9 @@ class Solve:
     # true-residual refresh period (None: PhiML's value for the method -- 50 for 'CG', 20 for 'CG-adaptive'; 0 = never)
     check_every: int = 10
     refresh_every: Optional[int] = None
+    # None or 'multigrid': CG preconditioned by one geometric multigrid V-cycle per iteration (pressure solves only; csrc/multigrid.hpp).
+    # The name is this backend's: PhiML's own preconditioner values are not mapped.
+    preconditioner: Optional[str] = None
 
     def with_defaults(self, fp64: bool) -> 'Solve':
         default = 1e-12 if fp64 else 1e-5
@@ -62,14 +65,27 @@ class Solve:
                        abs_tol=default if self.abs_tol is None else float(self.abs_tol), refresh_every=refresh)
 
     METHODS = {'auto': 0, 'CG': 0, 'CG-adaptive': 1}     # phihip_method (include/phihip.h)
+    PRECONDITIONERS = (None, 'multigrid')
+    METHOD_CG_MULTIGRID = 2                              # phihip_method of 'CG' / 'auto' with preconditioner='multigrid'
+
+    def c_method(self) -> int:
+        """ the `phihip_method` value of (method, preconditioner) """
+        if self.method not in self.METHODS:
+            raise NotImplementedError(f"HIP backend: Solve(method={self.method!r}) is not available, use one of {tuple(self.METHODS)}")
+        if self.preconditioner is None:
+            return self.METHODS[self.method]
+        if self.preconditioner not in self.PRECONDITIONERS:
+            raise NotImplementedError(f"HIP backend: Solve(preconditioner={self.preconditioner!r}) is not available, use one of {self.PRECONDITIONERS}")
+        if self.METHODS[self.method] != 0:
+            raise NotImplementedError(f"HIP backend: Solve(method={self.method!r}) takes no preconditioner; preconditioner='multigrid' goes with 'CG' or 'auto'")
+        return self.METHOD_CG_MULTIGRID
 
     def to_c(self, fp64: bool):
         """ the `phihip_solve` struct of this solve """
         from . import _capi
-        if self.method not in self.METHODS:
-            raise NotImplementedError(f"HIP backend: Solve(method={self.method!r}) is not available, use one of {tuple(self.METHODS)}")
+        method = self.c_method()
         s = self.with_defaults(fp64)
-        return _capi.Solve(s.rel_tol, s.abs_tol, int(s.max_iterations), int(s.refresh_every), int(s.check_every), self.METHODS[self.method])
+        return _capi.Solve(s.rel_tol, s.abs_tol, int(s.max_iterations), int(s.refresh_every), int(s.check_every), method)
 
     def with_preprocessing(self, preprocess_y: Callable, *args) -> 'Solve':
         return replace(self, preprocess_y=preprocess_y, preprocess_y_args=args)

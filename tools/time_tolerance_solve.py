@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """ wall time of tolerance-mode CG solves (host polls the device-side continue flags every `check_every` iterations):
-    python tools/time_tolerance_solve.py [--lib other/libphihip.so] """
+    python tools/time_tolerance_solve.py [--lib other/libphihip.so] [--preconditioner multigrid] """
 import argparse
 import json
 import os
@@ -17,6 +17,7 @@ from phiflow_amd import _capi as C   # noqa: E402
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--lib", default="")
+    ap.add_argument("--preconditioner", default="none", choices=["none", "multigrid"], help="multigrid: phihip_method 2 (Solve(preconditioner='multigrid'))")
     args = ap.parse_args()
     ctx = C.Context(C.Library(args.lib, strict=False) if args.lib else C.load_default_library(), 0)
     dev = torch.device("cuda:0")
@@ -27,7 +28,7 @@ def main():
         rhs -= rhs.mean(dim=tuple(range(1, rank + 1)), keepdim=True)
         rhs = rhs.to(dev)
         x = torch.zeros_like(rhs)
-        solve = C.Solve(rtol, 0.0, 20000, 50, 10, 0)
+        solve = C.Solve(rtol, 0.0, 20000, 50, 10, 2 if args.preconditioner == "multigrid" else 0)
         ctx.cg_solve(grid, 0, 1, rhs.data_ptr(), x.data_ptr(), solve)
         best = None
         for _ in range(3):
@@ -38,7 +39,7 @@ def main():
             dt = time.perf_counter() - t0
             best = dt if best is None else min(best, dt)
         its = max(i.iterations for i in info)
-        print(json.dumps({"lib": os.path.basename(args.lib) if args.lib else "default", "shape": shape, "batch": B, "rtol": rtol,
+        print(json.dumps({"lib": os.path.basename(args.lib) if args.lib else "default", "preconditioner": args.preconditioner, "shape": shape, "batch": B, "rtol": rtol,
                           "iterations": its, "converged": all(i.converged for i in info), "ms": round(best * 1e3, 3),
                           "us_per_iteration": round(best / its * 1e6, 2)}), flush=True)
 
