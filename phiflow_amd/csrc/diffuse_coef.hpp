@@ -281,8 +281,9 @@ static CoefOp coef_op(const GridView& v, const ScalarBc& ub, const void* coef, i
         for (int side = 0; side < 2; ++side) {
             op.ubc[a][side] = a < v.ax0 ? PHIHIP_BC_PERIODIC : ub.bc[a][side];
             op.uval[a][side] = ub.bc[a][side] == PHIHIP_BC_CLOSED ? ub.val[a][side] : 0.0;
-            op.cbc[a][side] = a < v.ax0 ? PHIHIP_BC_PERIODIC : cb.bc[a][side];
-            op.cval[a][side] = cb.val[a][side];
+            // no coefficient array: 1 everywhere, ghosts included -- the ghost is the cell's own 1 (zero-gradient), never u's wall constant
+            op.cbc[a][side] = a < v.ax0 ? PHIHIP_BC_PERIODIC : (coef != nullptr ? cb.bc[a][side] : PHIHIP_BC_OPEN);
+            op.cval[a][side] = coef != nullptr ? cb.val[a][side] : 1.0;
         }
     }
     op.has_c = coef != nullptr;

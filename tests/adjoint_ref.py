@@ -1,0 +1,360 @@
+"""
+TEST INFRASTRUCTURE: a differentiable restatement, in torch on the CPU, of the forward functions whose adjoints phiflow_amd/csrc/adjoint.hip
+writes by hand. Written from oracle/phi_oracle.py, function by function and in its order of operations, so that in float64 the forward values
+equal the oracle's to rounding (every user pins that: `pin`); the gradients then come from torch.autograd and are compared ELEMENT BY ELEMENT
+with the kernels' (tests/adjoint_cases.py).
+
+Conventions
+  * arrays are (batch, *spatial) like the oracle's; the element type is the inputs' (float64: the reference; float32: the same arithmetic at
+    the kernels' precision, to put a kernel's error next to what a plain float32 evaluation gives).
+  * boundary rules are the oracle's: PERIODIC wraps the index, OPEN clamps it, CLOSED is a constant tap (no gradient), staggered components
+    carry the wall values of the domain.
+  * `floor` is taken on the DETACHED coordinate: autograd differentiates the interpolation weights on the side of a cell boundary the point
+    lies on -- the kernels' convention (parity_cases.check_adjoint_next_to_a_lookup_kink).
+  * the limiter of MacCormack is amin / amax over the stacked taps and a clamp.
+Every function takes a `Margins` object and records how far its decisions were from flipping: the distance of every lookup coordinate from an
+integer (`coord`: the smallest one), and per sample of a MacCormack result the distance of the limiter's decision (`limiter`: min over
+|new - lo|, |new - hi| and the gaps between the extremal tap and the runner-up that is a different array element).
+"""
+import os
+
+import numpy as np
+import torch
+
+from oracle import phi_oracle as O
+
+PER, CLO, OPN = O.PERIODIC, O.CLOSED, O.OPEN
+if "PYTEST_XDIST_WORKER" in os.environ:
+    torch.set_num_threads(1)  # (small tensors, and the test workers already run side by side)
+
+
+class Margins:
+    def __init__(self):
+        self.coord = float('inf')       # smallest distance of a lookup coordinate from an integer (cells)
+        self.samples = 0                # lookups seen
+        self.limiter = []               # per MacCormack output array: tensor of the limiter's decision margin per sample
+
+    def see_coords(self, frac):
+        with torch.no_grad():
+            m = torch.minimum(frac, 1 - frac)
+            if m.numel():
+                self.coord = min(self.coord, float(m.min()))
+                self.samples += m.numel()
+
+
+def tensor(a, dtype=torch.float64, requires_grad=False):
+    t = torch.from_numpy(np.ascontiguousarray(np.asarray(a))).to(dtype).clone()
+    return t.requires_grad_(requires_grad)
+
+
+def _const(a, like):
+    """ a constant NumPy array of positions as a tensor of `like`'s element type """
+    return torch.from_numpy(np.ascontiguousarray(a)).to(like.dtype)
+
+
+def _np_dtype(t):
+    return np.float64 if t.dtype == torch.float64 else np.float32
+
+
+# ---- padding (oracle: _pad_axis, pad_component, pad_scalar) -------------------------------------------------------------------------------------
+def pad_axis(a, axis, lo, hi, code_lo, code_hi, c_lo, c_hi):
+    ax = axis + 1
+    n = a.shape[ax]
+    parts = []
+    for width, code, const, ids in ((lo, code_lo, c_lo, np.arange(-lo, 0)), (0, None, None, None), (hi, code_hi, c_hi, np.arange(n, n + hi))):
+        if code is None:
+            parts.append(a)
+        elif width > 0:
+            if code == PER:
+                parts.append(a.index_select(ax, torch.from_numpy(ids % n)))
+            elif code == OPN:
+                parts.append(a.index_select(ax, torch.from_numpy(np.clip(ids, 0, n - 1))))
+            else:
+                shp = list(a.shape)
+                shp[ax] = width
+                parts.append(torch.full(shp, float(const), dtype=a.dtype))
+    return torch.cat(parts, dim=ax) if len(parts) > 1 else a
+
+
+def pad_component(a, comp, widths, dom):
+    for axis, (lo, hi) in enumerate(widths):
+        if lo or hi:
+            a = pad_axis(a, axis, lo, hi, dom.bc[axis][0], dom.bc[axis][1], dom.bc_val[axis][0][comp], dom.bc_val[axis][1][comp])
+    return a
+
+
+def pad_scalar(a, widths, codes, consts):
+    for axis, (lo, hi) in enumerate(widths):
+        if lo or hi:
+            a = pad_axis(a, axis, lo, hi, codes[axis][0], codes[axis][1], consts[axis][0], consts[axis][1])
+    return a
+
+
+# ---- multilinear lookup (oracle: _tap, grid_sample, closest_limits) ------------------------------------------------------------------------------
+def tap(a, idx, codes, consts):
+    """ values of a (batch, *spatial) at the integer indices idx[axis] (batch, *pts); returns (values, element id, is-constant): the LAST axis
+    outside a constant side wins; the element id is the flat index of the array element a non-constant tap reads """
+    D, B = a.dim() - 1, a.shape[0]
+    shape = idx[0].shape
+    const_mask = torch.zeros(shape, dtype=torch.bool)
+    const_val = torch.zeros(shape, dtype=a.dtype)
+    flat = torch.zeros(shape, dtype=torch.long)
+    for axis in range(D):
+        n = a.shape[axis + 1]
+        i = idx[axis]
+        lo_code, hi_code = codes[axis]
+        if lo_code == PER:
+            j = torch.remainder(i, n)
+        else:
+            j = torch.clamp(i, 0, n - 1)
+            if lo_code == CLO:
+                const_val = torch.where(i < 0, torch.tensor(float(consts[axis][0]), dtype=a.dtype), const_val)
+                const_mask = const_mask | (i < 0)
+            if hi_code == CLO:
+                const_val = torch.where(i >= n, torch.tensor(float(consts[axis][1]), dtype=a.dtype), const_val)
+                const_mask = const_mask | (i >= n)
+        flat = flat * n + j
+    bidx = torch.arange(B).reshape((B,) + (1,) * (len(shape) - 1)).expand(shape)
+    per_entry = int(np.prod(a.shape[1:]))
+    vals = a.reshape(-1)[bidx * per_entry + flat]
+    return torch.where(const_mask, const_val, vals), flat, const_mask
+
+
+def _split(coords, margins):
+    fl = [torch.floor(c.detach()) for c in coords]
+    fr = [c - f for c, f in zip(coords, fl)]
+    if margins is not None:
+        for f in fr:
+            margins.see_coords(f.detach())
+    return [f.to(torch.long) for f in fl], fr
+
+
+def grid_sample(a, coords, codes, consts, margins=None):
+    D = a.dim() - 1
+    i0, fr = _split(coords, margins)
+    out = torch.zeros(coords[0].shape, dtype=a.dtype)
+    for corner in range(1 << D):
+        w = torch.ones(coords[0].shape, dtype=a.dtype)
+        idx = []
+        for axis in range(D):
+            bit = (corner >> axis) & 1
+            idx.append(i0[axis] + bit)
+            w = w * (fr[axis] if bit else (1 - fr[axis]))
+        out = out + tap(a, idx, codes, consts)[0] * w
+    return out
+
+
+def closest_limits(a, coords, codes, consts, margins=None):
+    """ (lo, hi, gap): amin / amax over the 2^D taps; gap = the distance from the extremal tap to the nearest tap that is ANOTHER array element
+    (two taps that clamp onto the same element, or two constants, cannot disagree about where the gradient goes) """
+    D = a.dim() - 1
+    i0, _ = _split(coords, margins)
+    taps, ids, cst = [], [], []
+    for corner in range(1 << D):
+        t, f, c = tap(a, [i0[axis] + ((corner >> axis) & 1) for axis in range(D)], codes, consts)
+        taps.append(t); ids.append(f); cst.append(c)
+    taps, ids, cst = torch.stack(taps), torch.stack(ids), torch.stack(cst)
+    lo, hi = taps.amin(0), taps.amax(0)
+    with torch.no_grad():
+        gap = torch.full(lo.shape, float('inf'), dtype=a.dtype)
+        for ext, pick in ((lo, taps.argmin(0, keepdim=True)), (hi, taps.argmax(0, keepdim=True))):
+            same = ((ids == ids.gather(0, pick)) & ~cst & ~cst.gather(0, pick)) | (cst & cst.gather(0, pick))
+            d = torch.where(same, torch.full_like(taps, float('inf')), (taps - ext[None]).abs())
+            gap = torch.minimum(gap, d.amin(0))
+    return lo, hi, gap
+
+
+# ---- staggered helpers (oracle: bake_component, component_at_faces, _index_coords, staggered_at_centers) ----------------------------------------------
+def _comp_rule(dom, comp):
+    return dom.bc, [(dom.bc_val[axis][0][comp], dom.bc_val[axis][1][comp]) for axis in range(dom.rank)]
+
+
+def _sl(D, ax, a, b):
+    s = [slice(None)] * (D + 1)
+    s[ax + 1] = slice(a, b)
+    return tuple(s)
+
+
+def component_at_faces(v, c, d, dom):
+    D = dom.rank
+    a = v[c]
+    off_c, off_d = dom.face_offset(c), dom.face_offset(d)
+    n_d = dom.comp_shape(d)
+    widths = [(0, 0)] * D
+    widths[c] = (off_c, dom.res[c] + 1 - off_c - a.shape[c + 1])
+    first_cell, last_cell = off_d - 1, off_d + n_d[d] - 1
+    widths[d] = (max(0, -first_cell), max(0, last_cell - (dom.res[d] - 1)))
+    res = pad_component(a, c, widths, dom)
+    start_d = first_cell + widths[d][0]
+    for axis in sorted((c, d)):
+        if axis == c:
+            lo, hi = _sl(D, axis, 0, dom.res[c]), _sl(D, axis, 1, dom.res[c] + 1)
+        else:
+            lo, hi = _sl(D, axis, start_d, start_d + n_d[d]), _sl(D, axis, start_d + 1, start_d + n_d[d] + 1)
+        res = res[hi] * 0.5 + res[lo] * 0.5
+    assert tuple(res.shape[1:]) == tuple(n_d)
+    return res
+
+
+def staggered_at_centers(v, dom):
+    D = dom.rank
+    out = []
+    for c in range(D):
+        lo, hi = dom.valid_faces(c)
+        widths = [(0, 0)] * D
+        widths[c] = (0 if lo else 1, 0 if hi else 1)
+        b = pad_component(v[c], c, widths, dom)
+        out.append(b[_sl(D, c, 1, dom.res[c] + 1)] * 0.5 + b[_sl(D, c, 0, dom.res[c])] * 0.5)
+    return out
+
+
+def _index_coords(points, comp, dom):
+    n, dx, off = dom.comp_shape(comp), dom.dx, dom.face_offset(comp)
+    out = []
+    for a in range(dom.rank):
+        lo = dom.lower[a] + ((off - 0.5) * dx[a] if a == comp else 0.0)
+        out.append((points[a] - lo) / (n[a] * dx[a]) * n[a] - 0.5)
+    return out
+
+
+def _cell_frame(points, dom):
+    return [(points[a] - dom.lower[a]) / (dom.upper[a] - dom.lower[a]) * dom.res[a] - 0.5 for a in range(dom.rank)]
+
+
+def _face_lookups(velocity, d, dt, dom, like):
+    """ end points of the stored faces of component d moved by dt * velocity (euler) """
+    D = dom.rank
+    pts = [_const(p, like) for p in O.face_positions(d, dom, _np_dtype(like))]
+    u = [velocity[d] if c == d else component_at_faces(velocity, c, d, dom) for c in range(D)]
+    return [pts[a][None] + u[a] * dt for a in range(D)]
+
+
+def _centre_lookups(velocity, dt, dom, like):
+    pts = [_const(p, like) for p in O.cell_positions(dom, _np_dtype(like))]
+    u = staggered_at_centers(velocity, dom)
+    return [pts[a][None] + u[a] * dt for a in range(dom.rank)]
+
+
+# ---- the forward functions ---------------------------------------------------------------------------------------------------------------------------------
+def semi_lagrangian_staggered(field, velocity, dt, dom, margins=None):
+    out = []
+    for d in range(dom.rank):
+        codes, consts = _comp_rule(dom, d)
+        out.append(grid_sample(field[d], _index_coords(_face_lookups(velocity, d, -dt, dom, field[d]), d, dom), codes, consts, margins))
+    return out
+
+
+def semi_lagrangian_centered(s, velocity, dt, dom, s_codes, s_consts, margins=None):
+    return grid_sample(s, _cell_frame(_centre_lookups(velocity, -dt, dom, s), dom), s_codes, s_consts, margins)
+
+
+def _limited(new, src, c_limits, codes, consts, margins):
+    lo, hi, gap = closest_limits(src, c_limits, codes, consts, margins)
+    if margins is not None:
+        with torch.no_grad():
+            margins.limiter.append(torch.minimum(torch.minimum((new - lo).abs(), (new - hi).abs()), gap))
+    return torch.where(new < lo, lo, torch.where(new > hi, hi, new))
+
+
+def mac_cormack_centered(s, velocity, dt, dom, s_codes, s_consts, strength=1.0, margins=None):
+    c_bwd = _cell_frame(_centre_lookups(velocity, -dt, dom, s), dom)
+    c_fwd = _cell_frame(_centre_lookups(velocity, dt, dom, s), dom)
+    fwd_adv = grid_sample(s, c_bwd, s_codes, s_consts, margins)
+    bwd_adv = grid_sample(fwd_adv, c_fwd, s_codes, s_consts, margins)
+    new = fwd_adv + (strength * 0.5) * (s - bwd_adv)
+    return _limited(new, s, c_bwd, s_codes, s_consts, margins)
+
+
+def mac_cormack_staggered(field, velocity, dt, dom, strength=1.0, margins=None):
+    """ the limiter window is taken in the CELL grid's index frame (half a cell off along the component's own axis), as the oracle documents """
+    out = []
+    for d in range(dom.rank):
+        codes, consts = _comp_rule(dom, d)
+        p_bwd, p_fwd = _face_lookups(velocity, d, -dt, dom, field[d]), _face_lookups(velocity, d, dt, dom, field[d])
+        fwd_adv = grid_sample(field[d], _index_coords(p_bwd, d, dom), codes, consts, margins)
+        bwd_adv = grid_sample(fwd_adv, _index_coords(p_fwd, d, dom), codes, consts, margins)
+        new = fwd_adv + (strength * 0.5) * (field[d] - bwd_adv)
+        out.append(_limited(new, field[d], _cell_frame(p_bwd, dom), codes, consts, margins))
+    return out
+
+
+def centered_to_staggered(s, dom, s_codes, s_consts, vector):
+    D = dom.rank
+    out = []
+    for d in range(D):
+        widths = [(0, 0)] * D
+        widths[d] = (1, 1)
+        p = pad_scalar(s, widths, s_codes, s_consts) * float(vector[d])
+        off, n = dom.face_offset(d), dom.comp_shape(d)[d]
+        out.append(p[_sl(D, d, off, off + n)] * 0.5 + p[_sl(D, d, off + 1, off + 1 + n)] * 0.5)
+    return out
+
+
+def diffuse_explicit(v, kdt, dom):
+    D = dom.rank
+    out = []
+    for comp, a in enumerate(v):
+        p = pad_component(a, comp, [(1, 1)] * D, dom)
+        core = tuple([slice(None)] + [slice(1, -1)] * D)
+        lap = torch.zeros_like(a)
+        for axis in range(D):
+            lo, hi = list(core), list(core)
+            lo[axis + 1], hi[axis + 1] = slice(0, -2), slice(2, None)
+            lap = lap + (p[tuple(lo)] + p[tuple(hi)] - 2 * p[core]) / (dom.dx[axis] ** 2)
+        out.append(a + kdt * lap)
+    return out
+
+
+def diffuse_explicit_centered(s, kdt, dom, s_codes, s_consts):
+    D = dom.rank
+    lap = torch.zeros_like(s)
+    for axis in range(D):
+        widths = [(0, 0)] * D
+        widths[axis] = (1, 1)
+        p = pad_scalar(s, widths, s_codes, s_consts)
+        lap = lap + (p[_sl(D, axis, 0, -2)] + p[_sl(D, axis, 2, None)] - 2 * p[_sl(D, axis, 1, -1)]) / (dom.dx[axis] ** 2)
+    return s + kdt * lap
+
+
+def diffuse_explicit_centered_coef(u, a, kdt, dx, u_codes, u_vals, a_codes=None, a_vals=None):
+    """ one explicit step in the conservative flux form with a coefficient field a (or None: 1) and per-axis factors kdt[d]: restates
+    tests/diffuse_coef_ref.py (face coefficient = min of the two cells', ghosts of `a` from its own extrapolation, wrapped where u is periodic) """
+    D = u.dim() - 1
+    if a is None:
+        a, a_codes, a_vals = torch.ones((1,) + tuple(u.shape[1:]), dtype=u.dtype), [(OPN, OPN)] * D, [(0.0, 0.0)] * D
+    a = a.expand(u.shape)
+    out = u
+    for d in range(D):
+        n = u.shape[d + 1]
+        w = kdt[d] / (dx[d] * dx[d])
+        ue = pad_axis(u, d, 1, 1, u_codes[d][0], u_codes[d][1], u_vals[d][0], u_vals[d][1])
+        wrap = u_codes[d][0] == PER
+        ae = pad_axis(a, d, 1, 1, PER if wrap else a_codes[d][0], PER if wrap else a_codes[d][1], a_vals[d][0], a_vals[d][1])
+        f = torch.minimum(w * ae[_sl(D, d, 0, n + 1)], w * ae[_sl(D, d, 1, n + 2)])
+        F = f * (ue[_sl(D, d, 1, n + 2)] - ue[_sl(D, d, 0, n + 1)])
+        out = out + (F[_sl(D, d, 1, n + 1)] - F[_sl(D, d, 0, n)])
+    return out
+
+
+# ---- pin and VJP -------------------------------------------------------------------------------------------------------------------------------------------------
+def pin(out, oracle_out, what):
+    """ the restatement is trusted through this: its float64 forward equals the oracle's float64 forward to 1e-12 of the largest element """
+    outs = out if isinstance(out, (list, tuple)) else [out]
+    refs = oracle_out if isinstance(oracle_out, (list, tuple)) else [oracle_out]
+    worst = 0.0
+    for a, b in zip(outs, refs):
+        b = np.asarray(b, np.float64)
+        err = float(np.abs(a.detach().numpy().astype(np.float64) - b).max()) / max(float(np.abs(b).max()), 1e-300) if b.size else 0.0
+        worst = max(worst, err)
+    assert worst <= 1e-12, f"{what}: the torch restatement is {worst:.2e} from the oracle's forward"
+    return worst
+
+
+def vjp(outs, cotangents, inputs):
+    """ gradient of sum(out * g) with respect to every input (zeros where an input does not reach the output) """
+    outs = outs if isinstance(outs, (list, tuple)) else [outs]
+    total = sum((o * g).sum() for o, g in zip(outs, cotangents))
+    if not total.requires_grad:
+        return [np.zeros(tuple(x.shape)) for x in inputs]
+    grads = torch.autograd.grad(total, inputs, allow_unused=True)
+    return [np.zeros(tuple(x.shape)) if g is None else g.numpy().astype(np.float64) for g, x in zip(grads, inputs)]

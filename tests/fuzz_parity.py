@@ -15,6 +15,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))   # this file lives there: test infrastructure (it drives the oracle)
+import adjoint_cases as ac           # noqa: E402
 import parity_cases as pc            # noqa: E402
 from phiflow_amd import _capi as C   # noqa: E402
 
@@ -116,6 +117,14 @@ def main():
             if dtype == np.float64 and min(res) >= 2:
                 step = "project_backward"; pc.check_project_backward(ctx, mem, dom, grid, rng)
                 step = "advect_backward"; pc.check_advect_backward(ctx, mem, dom, grid, rng, s_codes, s_consts, dt=float(r.uniform(0.1, 1.5)))
+            # element by element against torch.autograd through the float64 restatement (tests/adjoint_cases.py), in BOTH element types whatever the case's own
+            # is: the checks build their own velocities and wall values on the case's grid and boundary mix
+            adt = float(r.uniform(0.1, 3.0))
+            for edt in (np.float32, np.float64):
+                step = f"adjoint elementwise staggered {edt.__name__}"
+                ac.check_advect_staggered(ctx, mem, res, bc, edt, batch, adt, seed=seed, k0=int(r.integers(-1, 1)), slab_axis=int(r.integers(0, D)))
+                step = f"adjoint elementwise centred {edt.__name__}"
+                ac.check_advect_centered(ctx, mem, res, bc, edt, batch, adt, seed=seed, k0=int(r.integers(-1, 1)), slab_axis=int(r.integers(0, D)), flip=bool(r.integers(0, 2)))
             print("ok  ", tag, flush=True)
         except Exception as e:   # noqa: BLE001 -- report and go on
             fails += 1

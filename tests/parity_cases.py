@@ -896,12 +896,15 @@ def check_mac_cormack_and_diffuse_backward(ctx, mem, dom, grid, rng, s_codes, s_
     assert abs(lin - float(np.vdot(mem.to_host(gin_s), d))) <= 1e-10 * max(abs(lin), 1.0)
 
 
-def check_project_backward(ctx, mem, dom, grid, rng, obstacles=()):
+def check_project_backward(ctx, mem, dom, grid, rng, obstacles=(), dtype=np.float64):
     """ VJP of make_incompressible (velocity and pressure cotangents) against the oracle's forward: the map is affine, so the
-    directional derivative is the difference of two oracle projections. """
+    directional derivative is the difference of two oracle projections. `dtype` is the kernels' element type (that of `grid`): fp32 kernels get the
+    cotangents rounded to fp32 and are compared with the SAME float64 oracle difference, to the fp32 CG tolerance TOL32['cg_rel_l2'] (the
+    kernels' solve runs to the fp32 default of solve_params). """
+    kdtype = np.dtype(dtype)
     dtype = np.float64
     B, D = grid.batch, dom.rank
-    g_v = random_velocity(dom, B, dtype, rng)
+    g_v = [a.astype(kdtype).astype(dtype) for a in random_velocity(dom, B, dtype, rng)]
     g_p = rng.standard_normal((B,) + dom.res)
     flags_np = active = None
     dflags = None
@@ -917,12 +920,14 @@ def check_project_backward(ctx, mem, dom, grid, rng, obstacles=()):
         # (the singular system fixes p only up to its null space; use cotangents that do not see it)
         if active is not None:
             g_p = g_p - active * (g_p.sum(axis=tuple(range(1, g_p.ndim)), keepdims=True) / active.sum())
-    dgv = [mem.to_dev(a) for a in g_v]
-    dgp = mem.to_dev(g_p)
-    s = solve_params(dtype, rtol=1e-13)
+    g_p = g_p.astype(kdtype).astype(dtype)
+    dgv = [mem.to_dev(a.astype(kdtype)) for a in g_v]
+    dgp = mem.to_dev(g_p.astype(kdtype))
+    s = solve_params(dtype, rtol=1e-13) if kdtype == np.float64 else solve_params(np.float32)
     ctx.make_incompressible_backward(grid, mem.ptr(dflags) if dflags is not None else 0, 1, balance, [mem.ptr(a) for a in dgv], mem.ptr(dgp), s)
     mem.sync()
-    grad = [mem.to_host(a) for a in dgv]
+    grad = [mem.to_host(a).astype(dtype) for a in dgv]
+    bound = 1e-7 if kdtype == np.float64 else TOL32['cg_rel_l2']
 
     def forward(vel):   # projection WITHOUT the soft obstacle mask (that is a separate op with its own adjoint)
         hard_ = act_ = None
@@ -941,7 +946,7 @@ def check_project_backward(ctx, mem, dom, grid, rng, obstacles=()):
         (v1, p1), (v0, p0) = forward(d), forward(zero)
         lin = _dot(g_v, [a - b for a, b in zip(v1, v0)]) + float(np.vdot(g_p, p1 - p0))
         an = _dot(grad, d)
-        assert abs(lin - an) <= 1e-7 * max(abs(lin), abs(an), 1.0), f"make_incompressible_backward: oracle {lin} vs adjoint {an}"
+        assert abs(lin - an) <= bound * max(abs(lin), abs(an), 1.0), f"make_incompressible_backward ({kdtype.name}): oracle {lin} vs adjoint {an}"
 
 
 def check_slab_halo_planes(ctx, mem, dom, dtype, rng, parts=3):
