@@ -16,6 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))   # this file lives there: test infrastructure (it drives the oracle)
 import adjoint_cases as ac           # noqa: E402
+import multigrid_elementwise_cases as mgc   # noqa: E402
 import parity_cases as pc            # noqa: E402
 from phiflow_amd import _capi as C   # noqa: E402
 
@@ -125,6 +126,14 @@ def main():
                 ac.check_advect_staggered(ctx, mem, res, bc, edt, batch, adt, seed=seed, k0=int(r.integers(-1, 1)), slab_axis=int(r.integers(0, D)))
                 step = f"adjoint elementwise centred {edt.__name__}"
                 ac.check_advect_centered(ctx, mem, res, bc, edt, batch, adt, seed=seed, k0=int(r.integers(-1, 1)), slab_axis=int(r.integers(0, D)), flip=bool(r.integers(0, 2)))
+            # one multigrid V-cycle element by element against the float64 restatement of its recipe (tests/multigrid_ref.py) in fp64, whatever the case's
+            # element type: this case's grid and walls, random cell sizes, a random solid sphere more often than not (a PERIODIC axis of one cell is outside
+            # what the reference restates)
+            if not any(n == 1 and b == (PER, PER) for n, b in zip(res, bc)):
+                step = "multigrid cycle elementwise"
+                upper = tuple(float(n * r.uniform(0.3, 2.0)) for n in res)
+                ball = (tuple(float(r.uniform(0.2, 0.8)) * u for u in upper), float(r.uniform(0.1, 0.3)) * min(upper)) if r.random() < 0.7 else None
+                mgc.check_cycle_random(ctx, mem, res, bc, upper, ball, seed)
             print("ok  ", tag, flush=True)
         except Exception as e:   # noqa: BLE001 -- report and go on
             fails += 1
