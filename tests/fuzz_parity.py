@@ -16,6 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))   # this file lives there: test infrastructure (it drives the oracle)
 import adjoint_cases as ac           # noqa: E402
+import diffuse_coef_elementwise_cases as dce   # noqa: E402
 import multigrid_elementwise_cases as mgc   # noqa: E402
 import parity_cases as pc            # noqa: E402
 from phiflow_amd import _capi as C   # noqa: E402
@@ -134,6 +135,10 @@ def main():
                 upper = tuple(float(n * r.uniform(0.3, 2.0)) for n in res)
                 ball = (tuple(float(r.uniform(0.2, 0.8)) * u for u in upper), float(r.uniform(0.1, 0.3)) * min(upper)) if r.random() < 0.7 else None
                 mgc.check_cycle_random(ctx, mem, res, bc, upper, ball, seed)
+            # the first three iterations of diffuse.implicit's CG with a coefficient field, element by element against the float64 restatement
+            # (tests/diffuse_coef_ref.py) in fp64, whatever the case's element type: this case's grid and scalar walls, a refresh on the second iteration
+            step = "diffuse coef trajectory elementwise"
+            dce.check_cg_trajectory_random(ctx, mem, res, s_codes, seed)
             print("ok  ", tag, flush=True)
         except Exception as e:   # noqa: BLE001 -- report and go on
             fails += 1
