@@ -479,6 +479,37 @@ int phihip_set_autotune(phihip_ctx* ctx, int enable);
  * workgroup, workgroups per batch entry, resident workgroups per CU of that kernel, vector width} */
 int phihip_query_plan(phihip_ctx* ctx, const phihip_grid* grid, int has_flags, int family, int32_t out[6]);
 
+/* Grid differential operators, order 2. The centred gradient / divergence march over chunks of planes and the curl's forward pass over chunks of rows: a
+ * chunk_planes > 0 set with phihip_set_tuning_kernel(ctx, 0, ...) (the apply-type family) is taken as that chunk instead of the planned one.
+ * (phi/field/_field_math.py: laplace :46-145, spatial_gradient at='center' :229-233, divergence of a
+ * centred vector field :627-632, curl :642-673). The field is padded by one sample with its own extrapolation: PERIODIC wraps, OPEN
+ * (zero-gradient) copies the edge sample, CLOSED is the constant. Every *_backward entry (and adjoint != 0) ACCUMULATES the input gradient.
+ * laplace of a staggered field: out_d = weight * laplace(v_d) on the stored face lattice of every component with that component's wall
+ * constants (the lattices and rules of phihip_diffuse_explicit); adjoint != 0: out_d += weight * laplace_hom(velocity_d) (symmetric). */
+int phihip_field_laplace(phihip_ctx* ctx, const phihip_grid* grid, const void* const velocity[3], void* const out[3], double weight,
+                         int adjoint, void* stream);
+/* laplace of a centred scalar [batch][cells] (a centred vector field is the (batch * components) view): out = sum_d weights[d] d^2 s / dx_d^2 */
+int phihip_field_laplace_centered(phihip_ctx* ctx, const phihip_grid* grid, const void* s, const int32_t s_bc[3][2], const double s_val[3][2],
+                                  const double weights[3], void* out, int adjoint, void* stream);
+/* centred gradient of a centred scalar: out [batch][rank][cells], out_d = (S[i + e_d] - S[i - e_d]) / (2 dx_d) */
+int phihip_gradient_centered(phihip_ctx* ctx, const phihip_grid* grid, const void* s, const int32_t s_bc[3][2], const double s_val[3][2],
+                             void* out, void* stream);
+int phihip_gradient_centered_backward(phihip_ctx* ctx, const phihip_grid* grid, const int32_t s_bc[3][2], const void* grad_out, void* grad_s,
+                                      void* stream);
+/* centred divergence of a centred vector field [batch][rank][cells]: out = sum_d (V_d[i + e_d] - V_d[i - e_d]) / (2 dx_d) */
+int phihip_divergence_centered(phihip_ctx* ctx, const phihip_grid* grid, const void* field, const int32_t s_bc[3][2], const double s_val[3][2],
+                               void* out, void* stream);
+int phihip_divergence_centered_backward(phihip_ctx* ctx, const phihip_grid* grid, const int32_t s_bc[3][2], const void* grad_out,
+                                        void* grad_field, void* stream);
+/* curl of a 2-D vector field at the (nx + 1) x (ny + 1) cell corners, out [batch][nx + 1][ny + 1]. staggered != 0: vx [batch][nx + 1][ny] and
+ * vy [batch][nx][ny + 1] hold ALL faces; s_bc[0] / s_val[0] pad vy along x, s_bc[1] / s_val[1] pad vx along y;
+ * curl = (vy[i][j] - vy[i - 1][j]) / dx - (vx[i][j] - vx[i][j - 1]) / dy. staggered == 0: vx points at the centred field [batch][2][nx][ny], vy is
+ * NULL; curl = (vx - vy)[ll] - (vx + vy)[ul] + (vx + vy)[lr] - (vx - vy)[ur] over the four cells around the corner (no 1 / dx: as the reference). */
+int phihip_curl_2d(phihip_ctx* ctx, const phihip_grid* grid, int staggered, const void* vx, const void* vy, const int32_t s_bc[3][2],
+                   const double s_val[3][2], void* out, void* stream);
+int phihip_curl_2d_backward(phihip_ctx* ctx, const phihip_grid* grid, int staggered, const int32_t s_bc[3][2], const void* grad_out, void* grad_vx,
+                            void* grad_vy, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,6 +34,8 @@ EXPORTED_SYMBOLS = (
     "phihip_diffuse_explicit_centered_coef", "phihip_diffuse_implicit_centered_coef",
     "phihip_advect_centered_vector", "phihip_staggered_to_centered", "phihip_centered_vector_to_staggered",
     "phihip_precondition_apply", "phihip_set_multigrid", "phihip_query_multigrid",
+    "phihip_field_laplace", "phihip_field_laplace_centered", "phihip_gradient_centered", "phihip_gradient_centered_backward",
+    "phihip_divergence_centered", "phihip_divergence_centered_backward", "phihip_curl_2d", "phihip_curl_2d_backward",
 )
 
 
@@ -251,6 +253,15 @@ class Library:
         d.phihip_precondition_apply.argtypes = [c_void_p, POINTER(Grid), c_void_p, c_int, c_void_p, c_void_p, c_void_p]
         d.phihip_set_multigrid.argtypes = [c_void_p, c_int, c_int, c_int, c_double]
         d.phihip_query_multigrid.argtypes = [c_void_p, POINTER(c_int32 * 2)]
+        _bc, _val = POINTER((c_int32 * 2) * 3), POINTER((c_double * 2) * 3)
+        d.phihip_field_laplace.argtypes = [c_void_p, POINTER(Grid), POINTER(_Ptr3), POINTER(_Ptr3), c_double, c_int, c_void_p]
+        d.phihip_field_laplace_centered.argtypes = [c_void_p, POINTER(Grid), c_void_p, _bc, _val, POINTER(c_double * 3), c_void_p, c_int, c_void_p]
+        d.phihip_gradient_centered.argtypes = [c_void_p, POINTER(Grid), c_void_p, _bc, _val, c_void_p, c_void_p]
+        d.phihip_gradient_centered_backward.argtypes = [c_void_p, POINTER(Grid), _bc, c_void_p, c_void_p, c_void_p]
+        d.phihip_divergence_centered.argtypes = [c_void_p, POINTER(Grid), c_void_p, _bc, _val, c_void_p, c_void_p]
+        d.phihip_divergence_centered_backward.argtypes = [c_void_p, POINTER(Grid), _bc, c_void_p, c_void_p, c_void_p]
+        d.phihip_curl_2d.argtypes = [c_void_p, POINTER(Grid), c_int, c_void_p, c_void_p, _bc, _val, c_void_p, c_void_p]
+        d.phihip_curl_2d_backward.argtypes = [c_void_p, POINTER(Grid), c_int, _bc, c_void_p, c_void_p, c_void_p, c_void_p]
         for name in EXPORTED_SYMBOLS:
             if name not in ("phihip_version", "phihip_last_error", "phihip_build_id"):
                 getattr(d, name).restype = c_int
@@ -541,6 +552,44 @@ class Context:
         self.lib.check(self.lib.dll.phihip_diffuse_explicit_centered_coef(self.handle, ctypes.byref(grid), s, ctypes.byref(bc), ctypes.byref(val), coef or None,
                                                                           int(c_batch), ctypes.byref(cbc), ctypes.byref(cval), ctypes.byref(k), out,
                                                                           int(bool(adjoint)), stream or None))
+
+    # --- grid differential operators (csrc/diffops.hpp); adjoint / *_backward accumulate the input gradient ---
+    def field_laplace(self, grid, velocity, out, weight, adjoint=False, stream=0):
+        self.lib.check(self.lib.dll.phihip_field_laplace(self.handle, ctypes.byref(grid), ctypes.byref(ptr3(velocity)), ctypes.byref(ptr3(out)),
+                                                         float(weight), int(bool(adjoint)), stream or None))
+
+    def field_laplace_centered(self, grid, s, s_bc, s_val, weights, out, adjoint=False, stream=0):
+        bc, val = self._scalar_bc(grid, s_bc, s_val)
+        w = (c_double * 3)(*[float(x) for x in weights], *([0.0] * (3 - len(weights))))
+        self.lib.check(self.lib.dll.phihip_field_laplace_centered(self.handle, ctypes.byref(grid), s, ctypes.byref(bc), ctypes.byref(val), ctypes.byref(w), out,
+                                                                  int(bool(adjoint)), stream or None))
+
+    def gradient_centered(self, grid, s, s_bc, s_val, out, stream=0):
+        bc, val = self._scalar_bc(grid, s_bc, s_val)
+        self.lib.check(self.lib.dll.phihip_gradient_centered(self.handle, ctypes.byref(grid), s, ctypes.byref(bc), ctypes.byref(val), out, stream or None))
+
+    def gradient_centered_backward(self, grid, s_bc, grad_out, grad_s, stream=0):
+        bc, _ = self._scalar_bc(grid, s_bc, None)
+        self.lib.check(self.lib.dll.phihip_gradient_centered_backward(self.handle, ctypes.byref(grid), ctypes.byref(bc), grad_out, grad_s, stream or None))
+
+    def divergence_centered(self, grid, field, s_bc, s_val, out, stream=0):
+        bc, val = self._scalar_bc(grid, s_bc, s_val)
+        self.lib.check(self.lib.dll.phihip_divergence_centered(self.handle, ctypes.byref(grid), field, ctypes.byref(bc), ctypes.byref(val), out, stream or None))
+
+    def divergence_centered_backward(self, grid, s_bc, grad_out, grad_field, stream=0):
+        bc, _ = self._scalar_bc(grid, s_bc, None)
+        self.lib.check(self.lib.dll.phihip_divergence_centered_backward(self.handle, ctypes.byref(grid), ctypes.byref(bc), grad_out, grad_field, stream or None))
+
+    def curl_2d(self, grid, staggered, vx, vy, s_bc, s_val, out, stream=0):
+        """ staggered: vx / vy hold all faces; centred: vx is the (batch, 2, nx, ny) field and vy = 0 """
+        bc, val = self._scalar_bc(grid, s_bc, s_val)
+        self.lib.check(self.lib.dll.phihip_curl_2d(self.handle, ctypes.byref(grid), int(bool(staggered)), vx, vy or None, ctypes.byref(bc), ctypes.byref(val), out,
+                                                   stream or None))
+
+    def curl_2d_backward(self, grid, staggered, s_bc, grad_out, grad_vx, grad_vy, stream=0):
+        bc, _ = self._scalar_bc(grid, s_bc, None)
+        self.lib.check(self.lib.dll.phihip_curl_2d_backward(self.handle, ctypes.byref(grid), int(bool(staggered)), ctypes.byref(bc), grad_out, grad_vx,
+                                                            grad_vy or None, stream or None))
 
     def diffuse_implicit_centered_coef(self, grid, s, s_bc, s_val, coef, c_batch, c_bc, c_val, kdt, out, solve: Solve, stream=0, want_info=True):
         """ diffuse.implicit with a varying / per-axis diffusivity; returns [batch] SolveInfo (None with want_info=False: no host read-back) """

@@ -233,6 +233,121 @@ class DiffuseCentered(torch.autograd.Function):
         return None, gin
 
 
+# ---- grid differential operators (csrc/diffops.hpp): the backward entries accumulate into a zeroed buffer ------------------------------------------
+class LaplaceStaggered(torch.autograd.Function):
+    """ out_d = weight * laplace(v_d) per staggered component; the operator is symmetric: backward = the same stencil with homogeneous walls """
+
+    @staticmethod
+    def forward(ctx, meta, *vel):
+        v = [t.contiguous() for t in vel]
+        be = meta['be']
+        out = [be.empty(tuple(t.shape), t.dtype) for t in v]
+        be.ctx.field_laplace(meta['grid'], _ptrs(v), _ptrs(out), meta['weight'], False, be.stream())
+        ctx.meta = meta
+        ctx.like = [(tuple(t.shape), t.dtype) for t in v]
+        return tuple(out)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        meta = ctx.meta
+        be = meta['be']
+        g = [gi.contiguous() if gi is not None else be.zeros(shape, dtype) for gi, (shape, dtype) in zip(grads, ctx.like)]
+        gin = [torch.zeros_like(t) for t in g]
+        be.ctx.field_laplace(meta['grid'], _ptrs(g), _ptrs(gin), meta['weight'], True, be.stream())
+        return (None, *gin)
+
+
+class LaplaceCentered(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, meta, s):
+        s = s.contiguous()
+        be = meta['be']
+        out = be.empty(tuple(s.shape), s.dtype)
+        be.ctx.field_laplace_centered(meta['grid'], s.data_ptr(), meta['s_codes'], meta['s_val'], meta['weights'], out.data_ptr(), False, be.stream())
+        ctx.meta = meta
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        meta = ctx.meta
+        be = meta['be']
+        g = grad.contiguous()
+        gin = torch.zeros_like(g)
+        be.ctx.field_laplace_centered(meta['grid'], g.data_ptr(), meta['s_codes'], meta['s_val'], meta['weights'], gin.data_ptr(), True, be.stream())
+        return None, gin
+
+
+class GradientCentered(torch.autograd.Function):
+    """ (batch, *res) -> (batch, D, *res): central differences; backward = their true transpose (not the negative divergence at walls) """
+
+    @staticmethod
+    def forward(ctx, meta, s):
+        s = s.contiguous()
+        be = meta['be']
+        out = be.empty((s.shape[0], meta['rank']) + tuple(s.shape[1:]), s.dtype)
+        be.ctx.gradient_centered(meta['grid'], s.data_ptr(), meta['s_codes'], meta['s_val'], out.data_ptr(), be.stream())
+        ctx.meta = meta
+        ctx.shape = tuple(s.shape)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        meta = ctx.meta
+        be = meta['be']
+        g = grad.contiguous()
+        gin = be.zeros(ctx.shape, g.dtype)
+        be.ctx.gradient_centered_backward(meta['grid'], meta['s_codes'], g.data_ptr(), gin.data_ptr(), be.stream())
+        return None, gin
+
+
+class DivergenceCentered(torch.autograd.Function):
+    """ (batch, D, *res) -> (batch, *res) """
+
+    @staticmethod
+    def forward(ctx, meta, v):
+        v = v.contiguous()
+        be = meta['be']
+        out = be.empty((v.shape[0],) + tuple(v.shape[2:]), v.dtype)
+        be.ctx.divergence_centered(meta['grid'], v.data_ptr(), meta['s_codes'], meta['s_val'], out.data_ptr(), be.stream())
+        ctx.meta = meta
+        ctx.shape = tuple(v.shape)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        meta = ctx.meta
+        be = meta['be']
+        g = grad.contiguous()
+        gin = be.zeros(ctx.shape, g.dtype)
+        be.ctx.divergence_centered_backward(meta['grid'], meta['s_codes'], g.data_ptr(), gin.data_ptr(), be.stream())
+        return None, gin
+
+
+class Curl2D(torch.autograd.Function):
+    """ curl at the cell corners; inputs: all faces (vx, vy) of a staggered field, or the (batch, 2, nx, ny) values of a centred one """
+
+    @staticmethod
+    def forward(ctx, meta, *vel):
+        v = [t.contiguous() for t in vel]
+        be = meta['be']
+        out = be.empty(meta['shape'], v[0].dtype)
+        be.ctx.curl_2d(meta['grid'], meta['staggered'], v[0].data_ptr(), v[1].data_ptr() if meta['staggered'] else 0, meta['s_codes'], meta['s_val'],
+                       out.data_ptr(), be.stream())
+        ctx.meta = meta
+        ctx.like = [(tuple(t.shape), t.dtype) for t in v]
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        meta = ctx.meta
+        be = meta['be']
+        g = grad.contiguous()
+        gin = [be.zeros(shape, dtype) for shape, dtype in ctx.like]
+        be.ctx.curl_2d_backward(meta['grid'], meta['staggered'], meta['s_codes'], g.data_ptr(), gin[0].data_ptr(),
+                                gin[1].data_ptr() if meta['staggered'] else 0, be.stream())
+        return (None, *gin)
+
+
 class DiffuseCoefCentered(torch.autograd.Function):
     """ one substep of diffuse.explicit with a coefficient field / per-axis factors (csrc/diffuse_coef.hpp). The linear part of the operator is
     symmetric, so the vector-Jacobian product is the same stencil with homogeneous walls (adjoint flag: accumulated into gin). """

@@ -1263,4 +1263,86 @@ int phihip_set_tuning_kernel(phihip_ctx* ctx, int family, int rows_per_thread, i
     return PHIHIP_OK;
 }
 
+// ---- grid differential operators (diffops.hpp) ------------------------------------------------------------------------------------------------
+int phihip_field_laplace(phihip_ctx* ctx, const phihip_grid* grid, const void* const velocity[3], void* const out[3], double weight, int adjoint,
+                         void* stream) {
+    PHIHIP_ENTER(ctx, grid);
+    PHIHIP_TRY(check_ptrs(v, velocity, "velocity"));
+    PHIHIP_TRY(check_ptrs(v, (const void* const*)out, "out"));
+    PHIHIP_REQUIRE(weight == weight, "field_laplace: weight is NaN");
+    for (int d = 0; d < v.rank; ++d) PHIHIP_REQUIRE(out[d] != velocity[d], "field_laplace: out[%d] must not alias the input", d);
+    const void* u[3];
+    void* o[3];
+    remap3(v, velocity, u);
+    remap3w(v, out, o);
+    for (int d = v.ax0; d < 3; ++d) { note_align(v, u[d]); note_align(v, o[d]); }
+    return run_field_laplace(ctx, v, u, o, weight, adjoint, s);
+}
+
+int phihip_field_laplace_centered(phihip_ctx* ctx, const phihip_grid* grid, const void* sfield, const int32_t s_bc[3][2], const double s_val[3][2],
+                                  const double weights[3], void* out, int adjoint, void* stream) {
+    PHIHIP_ENTER(ctx, grid);
+    PHIHIP_REQUIRE(sfield && out && s_bc && weights && sfield != out, "field_laplace_centered: NULL or aliased argument");
+    PHIHIP_TRY(check_scalar_bc(v, s_bc, "field_laplace_centered"));
+    for (int d = 0; d < v.rank; ++d) PHIHIP_REQUIRE(weights[d] == weights[d], "field_laplace_centered: weights[%d] is NaN", d);
+    double w[3];
+    internal_kdt(v, weights, w);
+    note_align(v, sfield); note_align(v, out);
+    return run_field_laplace_centered(ctx, v, sfield, s_bc, s_val, w, out, adjoint, s);
+}
+
+int phihip_gradient_centered(phihip_ctx* ctx, const phihip_grid* grid, const void* sfield, const int32_t s_bc[3][2], const double s_val[3][2],
+                             void* out, void* stream) {
+    PHIHIP_ENTER(ctx, grid);
+    PHIHIP_REQUIRE(sfield && out && s_bc && sfield != out, "gradient_centered: NULL or aliased argument");
+    PHIHIP_TRY(check_scalar_bc(v, s_bc, "gradient_centered"));
+    return run_cgrad(ctx, v, sfield, s_bc, s_val, out, 0, s);
+}
+
+int phihip_gradient_centered_backward(phihip_ctx* ctx, const phihip_grid* grid, const int32_t s_bc[3][2], const void* grad_out, void* grad_s,
+                                      void* stream) {
+    PHIHIP_ENTER(ctx, grid);
+    PHIHIP_REQUIRE(grad_out && grad_s && s_bc && grad_out != grad_s, "gradient_centered_backward: NULL or aliased argument");
+    PHIHIP_TRY(check_scalar_bc(v, s_bc, "gradient_centered_backward"));
+    return run_cdiv(ctx, v, grad_out, s_bc, nullptr, grad_s, 1, s);
+}
+
+int phihip_divergence_centered(phihip_ctx* ctx, const phihip_grid* grid, const void* field, const int32_t s_bc[3][2], const double s_val[3][2],
+                               void* out, void* stream) {
+    PHIHIP_ENTER(ctx, grid);
+    PHIHIP_REQUIRE(field && out && s_bc && field != out, "divergence_centered: NULL or aliased argument");
+    PHIHIP_TRY(check_scalar_bc(v, s_bc, "divergence_centered"));
+    return run_cdiv(ctx, v, field, s_bc, s_val, out, 0, s);
+}
+
+int phihip_divergence_centered_backward(phihip_ctx* ctx, const phihip_grid* grid, const int32_t s_bc[3][2], const void* grad_out, void* grad_field,
+                                        void* stream) {
+    PHIHIP_ENTER(ctx, grid);
+    PHIHIP_REQUIRE(grad_out && grad_field && s_bc && grad_out != grad_field, "divergence_centered_backward: NULL or aliased argument");
+    PHIHIP_TRY(check_scalar_bc(v, s_bc, "divergence_centered_backward"));
+    return run_cgrad(ctx, v, grad_out, s_bc, nullptr, grad_field, 1, s);
+}
+
+int phihip_curl_2d(phihip_ctx* ctx, const phihip_grid* grid, int staggered, const void* vx, const void* vy, const int32_t s_bc[3][2],
+                   const double s_val[3][2], void* out, void* stream) {
+    PHIHIP_ENTER(ctx, grid);
+    PHIHIP_REQUIRE(v.rank == 2, "curl_2d: the grid must be 2-D (got rank %d)", v.rank);
+    PHIHIP_REQUIRE(vx && out && s_bc && out != vx && out != vy, "curl_2d: NULL or aliased argument");
+    PHIHIP_REQUIRE(staggered ? vy != nullptr : vy == nullptr, "curl_2d: vy must be given for a staggered field and NULL for a centred one");
+    PHIHIP_TRY(check_scalar_bc(v, s_bc, "curl_2d"));
+    const void* b = staggered ? vy : (const void*)((const char*)vx + (size_t)v.cells * (v.dtype == PHIHIP_F64 ? 8 : 4));
+    return run_curl2d(ctx, v, staggered, s_bc, s_val, 0, vx, b, out, nullptr, s);
+}
+
+int phihip_curl_2d_backward(phihip_ctx* ctx, const phihip_grid* grid, int staggered, const int32_t s_bc[3][2], const void* grad_out, void* grad_vx,
+                            void* grad_vy, void* stream) {
+    PHIHIP_ENTER(ctx, grid);
+    PHIHIP_REQUIRE(v.rank == 2, "curl_2d_backward: the grid must be 2-D (got rank %d)", v.rank);
+    PHIHIP_REQUIRE(grad_out && grad_vx && s_bc && grad_out != grad_vx && grad_out != grad_vy, "curl_2d_backward: NULL or aliased argument");
+    PHIHIP_REQUIRE(staggered ? grad_vy != nullptr : grad_vy == nullptr, "curl_2d_backward: grad_vy must be given for a staggered field and NULL for a centred one");
+    PHIHIP_TRY(check_scalar_bc(v, s_bc, "curl_2d_backward"));
+    void* b = staggered ? grad_vy : (void*)((char*)grad_vx + (size_t)v.cells * (v.dtype == PHIHIP_F64 ? 8 : 4));
+    return run_curl2d(ctx, v, staggered, s_bc, nullptr, 1, grad_out, nullptr, grad_vx, b, s);
+}
+
 }  // extern "C"

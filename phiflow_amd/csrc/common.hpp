@@ -392,6 +392,14 @@ int run_diffuse_coef_explicit(phihip_ctx*, const GridView&, const void* u, const
 int run_diffuse_coef_implicit(phihip_ctx*, const GridView&, const void* u, const int32_t s_bc[3][2], const double s_val[3][2], const void* coef, int c_batch,
                               const int32_t c_bc[3][2], const double c_val[3][2], const double kdt[3], const phihip_solve* solve, phihip_solve_info* info,
                               void* out, hipStream_t);
+// grid differential operators (diffops.hpp, compiled through project.hip); weights per INTERNAL axis
+int run_field_laplace(phihip_ctx*, const GridView&, const void* const v[3], void* const out[3], double weight, int adjoint, hipStream_t);
+int run_field_laplace_centered(phihip_ctx*, const GridView&, const void* s, const int32_t s_bc[3][2], const double s_val[3][2], const double weights[3],
+                               void* out, int adjoint, hipStream_t);
+int run_cgrad(phihip_ctx*, const GridView&, const void* in, const int32_t s_bc[3][2], const double s_val[3][2], void* out, int adjoint, hipStream_t);
+int run_cdiv(phihip_ctx*, const GridView&, const void* in, const int32_t s_bc[3][2], const double s_val[3][2], void* out, int adjoint, hipStream_t);
+int run_curl2d(phihip_ctx*, const GridView&, int staggered, const int32_t s_bc[3][2], const double s_val[3][2], int adjoint, const void* a, const void* b,
+               void* oa, void* ob, hipStream_t);
 int run_laplace_apply(phihip_ctx*, const GridView&, const uint8_t* flags, int mask_batch, const void* p, void* out, hipStream_t);
 int run_laplace_apply_multi(phihip_ctx*, const GridView* lattices, int count, const void* const* in, void* const* out, hipStream_t);   // MODE_APPLY, no flags: lattices of one tile configuration share a launch
 // host scaffolding of the CG drivers (cg.hip; diffuse_coef.hpp reaches it from project.hip's translation unit)

@@ -40,7 +40,8 @@ enum CoefMode {
     CM_MATVEC = 3,   // S = a + beta b ; o1 = S ; part1 = sum S (S + L S), part2 = sum S a ('CG-adaptive': d.r)
     CM_UPDATE = 4,   // S = a ; q = S + L S ; o1 += alpha S ; o2 -= alpha q ; part1 = sum o2^2, part2 = sum o2 q
     CM_AXPY = 5,     // o1 += alpha a (the true-residual refresh step: x only)
-    CM_DOTQ = 6      // S = a ; part1 = sum b (S + L S)  ('CG-adaptive' refresh: r_new . A d)
+    CM_DOTQ = 6,     // S = a ; part1 = sum b (S + L S)  ('CG-adaptive' refresh: r_new . A d)
+    CM_LAP = 7       // o1 = L S without the identity term (accumulate: o1 += ...), S = a: field.laplace (diffops.hpp) -- an instantiation of its own
 };
 
 struct CoefOp {
@@ -202,6 +203,9 @@ __global__ __launch_bounds__(kBlock) void coef_kernel(CoefOp op, CoefArgs<T> p) 
                 const T q = s_cur + lap;
                 if (p.accumulate) p.o1[bb + ic] += q;
                 else p.o1[bb + ic] = q;
+            } else if (MODE == CM_LAP) {
+                if (p.accumulate) p.o1[bb + ic] += lap;
+                else p.o1[bb + ic] = lap;
             } else if (MODE == CM_RHS) {
                 p.o1[bb + ic] = A[ic] - lap;
             } else if (MODE == CM_RESID) {

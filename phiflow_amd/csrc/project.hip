@@ -1775,3 +1775,5 @@ int run_diffuse_implicit_centered(phihip_ctx* ctx, const GridView& v, const void
 }
 
 }  // namespace phihip
+
+#include "diffops.hpp"

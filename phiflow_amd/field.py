@@ -244,6 +244,22 @@ class Field:
         return self._op(other, lambda a, b: a / b)
     def __neg__(self): return self._op(-1.0, lambda a, b: a * b)
 
+    def __pow__(self, exponent):
+        """ `u ** 2` (a number exponent, elementwise; Reaction_Diffusion.ipynb's `u * v ** 2`) """
+        if not isinstance(exponent, (int, float)):
+            raise NotImplementedError(f"Field ** {type(exponent).__name__}: only number exponents are implemented")
+        require_plain(self, '**')
+        return self._op(exponent, lambda a, b: a ** b)
+
+    def laplace(self, axes=None, weights=None, order: int = 2) -> 'Field':
+        return laplace(self, axes, weights, order)
+
+    def divergence(self, order: int = 2) -> 'Field':
+        return divergence(self, order)
+
+    def curl(self, at: str = 'corner') -> 'Field':
+        return curl(self, at)
+
     def at_centers(self) -> 'Field':
         """ `field.at_centers()`: the field sampled at the cell centres of its grid -- a centred vector field for a staggered one
         (phi/field/_field.py, _resample.py:241-259), the field itself when it is centred """
@@ -502,10 +518,12 @@ def _ptrs(tensors: Sequence[torch.Tensor]) -> List[int]:
 
 def divergence(field: Field, order: int = 2) -> Field:
     """ `field.divergence` of a StaggeredGrid, order 2 (phi/field/_field_math.py:589,617-626) -> CenteredGrid with
-    extrapolation `field.extrapolation.spatial_gradient()`. """
+    extrapolation `field.extrapolation.spatial_gradient()`; of a centred vector field the central differences of :627-632. """
     require_plain(field, 'divergence')
+    if order == 2 and field.is_vector:
+        return _divergence_centered(field)
     if order != 2 or not field.is_staggered:
-        raise NotImplementedError("the HIP backend implements divergence for StaggeredGrid, order=2 only")
+        raise NotImplementedError("the HIP backend implements divergence for a StaggeredGrid or a centred vector field, order=2 only")
     be = field.backend
     vals = [t.contiguous() for t in field.values]
     out = be.empty((field.batch_size,) + tuple(field.resolution.values()), field.dtype)
@@ -515,11 +533,14 @@ def divergence(field: Field, order: int = 2) -> Field:
 
 def spatial_gradient(field: Field, boundary=None, at: str = 'face', order: int = 2) -> Field:
     """ `field.spatial_gradient(p, boundary, at='face')` (phi/field/_field_math.py:148-236): gradient of a centred scalar
-    at the faces that a StaggeredGrid with `boundary` stores; `field.boundary` pads p. """
+    at the faces that a StaggeredGrid with `boundary` stores; `field.boundary` pads p. at='center' (the reference's default; the mirror's stays
+    'face'): the central differences of :229-233 as a centred vector field. """
     require_plain(field, 'spatial_gradient')
     require_centered_scalar(field, 'spatial_gradient')
-    if at != 'face' or order != 2 or field.is_staggered:
-        raise NotImplementedError("the HIP backend implements spatial_gradient(at='face', order=2) of a CenteredGrid only")
+    if at not in ('face', 'center') or order != 2 or field.is_staggered:
+        raise NotImplementedError("the HIP backend implements spatial_gradient(at='face' | 'center', order=2) of a scalar CenteredGrid only")
+    if at == 'center':
+        return _gradient_centered(field, boundary)
     vb = as_extrapolation(boundary if boundary is not None else field.boundary.spatial_gradient())
     be = field.backend
     proto = Field(field.resolution, field.bounds, vb, None, True, be, field.batched)
@@ -541,6 +562,203 @@ def _check_pressure_padding(p_ext: Extrapolation, v_ext: Extrapolation, dims):
             if type(have) is not type(want) or (isinstance(have, ConstantExtrapolation) and have.component_value(0, d) != 0):
                 raise NotImplementedError(f"gradient at faces: scalar extrapolation {have} on side {d}{'+' if upper else '-'} is not the one "
                                           f"the staggered boundary implies ({want}); only the pressure/velocity pairing is implemented")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# differential operators at the sample points (csrc/diffops.hpp), order 2
+# ---------------------------------------------------------------------------------------------------------------------
+def _cell_grid(field: Field, batch: Optional[int] = None) -> _capi.Grid:
+    """ descriptor of the cell grid of a centred field: it carries the periodicity only, the field's own rule travels as s_bc / s_val """
+    codes = resolve(field.boundary, field.dims)[0]
+    return _capi.make_grid(field.spatial_rank, _torch_dtype_code(field.dtype), batch or field.batch_size, list(field.resolution.values()),
+                           field.bounds.lower, field.bounds.upper, [[0 if c == 0 else 2 for c in pair] for pair in codes])
+
+
+def _difference_extrapolation(ext: Extrapolation, dims) -> Extrapolation:
+    """ extrapolation of `right - left` of two shifted copies of a field (phi/field/_field.py:791-795): PERIODIC stays, a constant becomes ZERO,
+    ZERO_GRADIENT stays (PhiML's rule for the last, recalled: PhiML is not installed) """
+    from .extrapolation import _Mixed
+    sides = {d: tuple(ZERO if isinstance(ext.side(d, up), ConstantExtrapolation) else ext.side(d, up) for up in (False, True)) for d in dims}
+    kinds = {repr(e) for pair in sides.values() for e in pair}
+    return next(iter(sides.values()))[0] if len(kinds) == 1 else _Mixed(sides)
+
+
+def _check_diff_rank(field: Field, what: str):
+    if field.spatial_rank not in (2, 3):
+        raise NotImplementedError(f"HIP backend: {what} on {field.spatial_rank}-D grids is not implemented (2-D and 3-D only)")
+
+
+def _laplace_weights(u: Field, axes, weights) -> List[float]:
+    """ per-axis factors of the laplace's axis terms: `weights` (None | number | per-axis vec / tuple) on the axes in `axes`, 0 elsewhere """
+    if isinstance(weights, Field):
+        raise NotImplementedError("laplace: a Field as `weights` is not implemented (a number or a per-axis vec(...) / tuple)")
+    if weights is None:
+        w = [1.0] * u.spatial_rank
+    elif isinstance(weights, Vector):
+        missing = [d for d in u.dims if d not in weights]
+        if missing:
+            raise ValueError(f"laplace: the weights {dict(weights)} have no component for {missing}")
+        w = [float(weights[d]) for d in u.dims]
+    elif isinstance(weights, (tuple, list)):
+        if len(weights) != u.spatial_rank:
+            raise ValueError(f"laplace: {len(weights)} weights for a {u.spatial_rank}-D field")
+        w = [float(k) for k in weights]
+    else:
+        w = [float(weights)] * u.spatial_rank
+    if axes is None or callable(axes):        # (`spatial`: every axis)
+        return w
+    names = [a.strip() for a in axes.split(',')] if isinstance(axes, str) else list(axes)
+    unknown = [a for a in names if a not in u.dims]
+    if unknown:
+        raise ValueError(f"laplace: axes {unknown} are not dimensions of {u!r}")
+    return [k if d in names else 0.0 for k, d in zip(w, u.dims)]
+
+
+def laplace(u: Field, axes=None, weights=None, order: int = 2) -> Field:
+    """ `field.laplace(u, axes, weights)` (phi/field/_field_math.py:46-145, grid branch :119-145), order 2:
+    sum over the axes of w_d (U[i + e_d] + U[i - e_d] - 2 U[i]) / dx_d^2 on every lattice of the field -- a centred scalar, every component of a
+    centred vector field, every component of a StaggeredGrid on its own faces with that component's wall constant -- U being the field padded
+    with its own extrapolation. Result: the same kind of field with `u.extrapolation.spatial_gradient().spatial_gradient()`.
+    Per-axis weights and axis subsets are for centred fields. Differentiable w.r.t. u. """
+    from . import autodiff
+    require_plain(u, 'laplace')
+    if order != 2:
+        raise NotImplementedError("HIP backend: laplace implements order=2 only")
+    w = _laplace_weights(u, axes, weights)
+    lap_ext = u.boundary.spatial_gradient().spatial_gradient()
+    be = u.backend
+    if u.is_staggered:
+        if any(k != w[0] for k in w):
+            raise NotImplementedError("laplace: per-axis weights / an axis subset need a CenteredGrid (as in diffuse)")
+        vals = [t.contiguous() for t in u.values]
+        if autodiff.needs_grad(*vals):
+            out = list(autodiff.LaplaceStaggered.apply(dict(be=be, grid=u.grid_struct(), weight=w[0]), *vals))
+        else:
+            out = [be.empty(tuple(t.shape), u.dtype) for t in vals]
+            be.ctx.field_laplace(u.grid_struct(), _ptrs(vals), _ptrs(out), w[0], False, be.stream())
+        return u.with_values(out).with_boundary(lap_ext)        # (re-stores the faces: BOUNDARY -> ZERO drops the outer ones, _field_math.py:145)
+    _check_diff_rank(u, 'laplace')
+    if u.is_vector:
+        require_scalar_boundary(u.boundary, u.dims, 'laplace')
+    s_codes, s_val = _centered_rule(u, 'laplace')
+    src = u.values.contiguous()
+    folded = src.reshape(-1, *src.shape[-u.spatial_rank:])      # a centred vector field: the (B * C, *res) view
+    meta = dict(be=be, grid=_cell_grid(u, folded.shape[0]), s_codes=s_codes, s_val=s_val, weights=w)
+    if autodiff.needs_grad(folded):
+        out = autodiff.LaplaceCentered.apply(meta, folded)
+    else:
+        out = be.empty(tuple(folded.shape), u.dtype)
+        be.ctx.field_laplace_centered(meta['grid'], folded.data_ptr(), s_codes, s_val, w, out.data_ptr(), False, be.stream())
+    return Field(u.resolution, u.bounds, lap_ext, out.reshape(src.shape), False, be, u.batched, vector=u.is_vector)
+
+
+def _gradient_centered(s: Field, boundary) -> Field:
+    """ g_d = (S[i + e_d] - S[i - e_d]) / (2 dx_d), S padded with the scalar's extrapolation -> centred vector field """
+    from . import autodiff
+    _check_diff_rank(s, "spatial_gradient(at='center')")
+    ext = as_extrapolation(boundary) if boundary is not None else s.boundary.spatial_gradient()
+    be = s.backend
+    s_codes, s_val = _centered_rule(s, 'spatial_gradient')
+    src = s.values.contiguous()
+    meta = dict(be=be, grid=_cell_grid(s), s_codes=s_codes, s_val=s_val, rank=s.spatial_rank)
+    if autodiff.needs_grad(src):
+        out = autodiff.GradientCentered.apply(meta, src)
+    else:
+        out = be.empty((s.batch_size, s.spatial_rank) + tuple(s.resolution.values()), s.dtype)
+        be.ctx.gradient_centered(meta['grid'], src.data_ptr(), s_codes, s_val, out.data_ptr(), be.stream())
+    return Field(s.resolution, s.bounds, ext, out, False, be, s.batched, vector=True)
+
+
+def _divergence_centered(v: Field) -> Field:
+    """ sum_d (V_d[i + e_d] - V_d[i - e_d]) / (2 dx_d), every component padded with the field's extrapolation -> centred scalar """
+    from . import autodiff
+    _check_diff_rank(v, 'divergence')
+    be = v.backend
+    s_codes, s_val = _centered_rule(v, 'divergence')
+    src = v.values.contiguous()
+    meta = dict(be=be, grid=_cell_grid(v), s_codes=s_codes, s_val=s_val)
+    if autodiff.needs_grad(src):
+        out = autodiff.DivergenceCentered.apply(meta, src)
+    else:
+        out = be.empty((v.batch_size,) + tuple(v.resolution.values()), v.dtype)
+        be.ctx.divergence_centered(meta['grid'], src.data_ptr(), s_codes, s_val, out.data_ptr(), be.stream())
+    return Field(v.resolution, v.bounds, _difference_extrapolation(v.boundary, v.dims), out, False, be, v.batched)
+
+
+def curl(v: Field, at: str = 'corner') -> Field:
+    """ `field.curl(v, at='corner')` of a 2-D vector field (phi/field/_field_math.py:642-673): sampled at the (nx + 1) x (ny + 1) cell corners and
+    returned as the CenteredGrid whose cell centres are the corners (resolution n + 1, bounds grown by dx / 2), extrapolation
+    `v.boundary.spatial_gradient()`.
+    Staggered: (vy[i, j] - vy[i - 1, j]) / dx - (vx[i, j] - vx[i, j - 1]) / dy on all n + 1 faces per axis, vx padded along y and vy along x. As in
+    the reference, vx is padded with the boundary's y COMPONENT and vy with its x component (:655-656) -- the other component of a vector-valued
+    constant; no difference for scalar-valued boundaries.
+    Centred: (vx - vy)[ll] - (vx + vy)[ul] + (vx + vy)[lr] - (vx - vy)[ur] over the four cells around the corner, WITHOUT the factors 1 / dx and
+    1 / 2 (as the reference): on square cells 2 dx times the staggered form. 3-D fields and other locations are not implemented. """
+    from . import autodiff
+    require_plain(v, 'curl')
+    if not (v.is_staggered or v.is_vector):
+        raise ValueError(f"curl requires a vector field but got {v!r}")
+    if v.spatial_rank != 2 or at != 'corner':
+        raise NotImplementedError("HIP backend: curl is implemented for 2-D vector fields at='corner' only")
+    be = v.backend
+    x, y = v.dims
+    dx = v.dx
+    res = {d: n + 1 for d, n in v.resolution.items()}
+    bounds = Box(**{d: (lo - 0.5 * h, up + 0.5 * h) for d, lo, up, h in zip(v.dims, v.bounds.lower, v.bounds.upper, dx)})
+    codes, vals = resolve(v.boundary, v.dims)
+    grid = _cell_grid(v)
+    shape = (v.batch_size, res[x], res[y])
+    if v.is_staggered:
+        baked = v.with_boundary(BOUNDARY)        # all n + 1 faces per axis, the missing ones from the field's own rule
+        vx, vy = [t.contiguous() for t in baked.values]
+        # vy is padded along x with the constant's x component, vx along y with its y component (the reference's literal choice)
+        s_val = [[vals[0][s][0] for s in range(2)], [vals[1][s][1] for s in range(2)]]
+        meta = dict(be=be, grid=grid, staggered=True, s_codes=codes, s_val=s_val, shape=shape)
+        if autodiff.needs_grad(vx, vy):
+            out = autodiff.Curl2D.apply(meta, vx, vy)
+        else:
+            out = be.empty(shape, v.dtype)
+            be.ctx.curl_2d(grid, True, vx.data_ptr(), vy.data_ptr(), codes, s_val, out.data_ptr(), be.stream())
+    else:
+        s_codes, s_val = _centered_rule(v, 'curl')
+        src = v.values.contiguous()
+        meta = dict(be=be, grid=grid, staggered=False, s_codes=s_codes, s_val=s_val, shape=shape)
+        if autodiff.needs_grad(src):
+            out = autodiff.Curl2D.apply(meta, src)
+        else:
+            out = be.empty(shape, v.dtype)
+            be.ctx.curl_2d(grid, False, src.data_ptr(), 0, s_codes, s_val, out.data_ptr(), be.stream())
+    return Field(res, bounds, v.boundary.spatial_gradient(), out, False, be, v.batched)
+
+
+def where(mask, a, b) -> Field:
+    """ `field.where(mask_or_geometry, a, b)` on one grid (phi/field/_field_math.py:997-1015): `a` where the mask is non-zero, else `b`. A
+    Geometry is rasterised to a hard mask on the grid of the first Field among a, b; numbers broadcast. """
+    proto = next((f for f in (a, b, mask) if isinstance(f, Field)), None)
+    if proto is None:
+        raise ValueError("where: at least one of the arguments must be a Field")
+    require_plain(proto, 'where')
+    if isinstance(mask, Geometry):
+        mask = resample(mask, to=proto)
+
+    def vals(f):
+        if not isinstance(f, Field):
+            return [f] * proto.spatial_rank if proto.is_staggered else f
+        require_plain(f, 'where')
+        assert f.is_staggered == proto.is_staggered and same_grid(f, proto), f"where: fields on different sample points: {f!r} vs {proto!r}"
+        if f.is_vector != proto.is_vector:      # a centred scalar against a centred vector: broadcast over the components
+            return f.values.unsqueeze(1) if proto.is_vector else f.values
+        return f.values
+    m, va, vb = vals(mask), vals(a), vals(b)
+
+    def pick(mm, xa, xb):
+        cond = mm != 0 if isinstance(mm, torch.Tensor) else torch.as_tensor(bool(mm), device=proto.backend.device)
+        xa = xa if isinstance(xa, torch.Tensor) else torch.as_tensor(float(xa), dtype=proto.dtype, device=proto.backend.device)
+        xb = xb if isinstance(xb, torch.Tensor) else torch.as_tensor(float(xb), dtype=proto.dtype, device=proto.backend.device)
+        return torch.where(cond, xa, xb)
+    out = [pick(mm, xa, xb) for mm, xa, xb in zip(m, va, vb)] if proto.is_staggered else pick(m, va, vb)
+    batched = any(isinstance(f, Field) and f.batched for f in (mask, a, b))
+    return Field(proto.resolution, proto.bounds, proto.boundary, out, proto.is_staggered, proto.backend, batched, vector=proto.is_vector)
 
 
 def mean(field: Field):

@@ -7,7 +7,8 @@ from . import extrapolation
 from .autodiff import functional_gradient, gradient, jacobian, l2_loss, stop_gradient
 from .backend import HipBackend, default_backend, precision, set_global_default_backend, set_global_precision
 from .extrapolation import BOUNDARY, ONE, PERIODIC, ZERO, ZERO_GRADIENT, ConstantExtrapolation, combine_sides
-from .field import CenteredGrid, Field, StaggeredGrid, assert_close, divergence, mean, resample, spatial_gradient
+from . import field
+from .field import CenteredGrid, Field, StaggeredGrid, assert_close, curl, divergence, laplace, mean, resample, spatial_gradient, where
 from .noise import Noise
 from . import geom
 from .geom import Box, Cuboid, Sphere, embed, infinite_cylinder, union, vec
@@ -21,6 +22,7 @@ __all__ = [
     'HipBackend', 'default_backend', 'precision', 'set_global_default_backend', 'set_global_precision',
     'BOUNDARY', 'ONE', 'PERIODIC', 'ZERO', 'ZERO_GRADIENT', 'ConstantExtrapolation', 'combine_sides',
     'CenteredGrid', 'Field', 'StaggeredGrid', 'Noise', 'assert_close', 'divergence', 'mean', 'resample', 'spatial_gradient',
+    'field', 'laplace', 'curl', 'where',
     'geom', 'Box', 'Cuboid', 'Sphere', 'embed', 'infinite_cylinder', 'union', 'vec', 'Obstacle',
     'functional_gradient', 'gradient', 'jacobian', 'l2_loss', 'stop_gradient',
     'ConvergenceException', 'Diverged', 'NotConverged', 'Solve', 'SolveInfo', 'copy_with', 'solve_linear',
