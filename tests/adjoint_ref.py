@@ -336,6 +336,111 @@ def diffuse_explicit_centered_coef(u, a, kdt, dx, u_codes, u_vals, a_codes=None,
     return out
 
 
+# ---- per-sample margins and evaluation at perturbed coordinates (tests/advect_forward_cases.py) ---------------------------------------------------------------
+def coord_distance(coords):
+    """ per axis and per sample: the distance of a lookup coordinate from the nearest integer (the per-sample form of Margins.coord) """
+    return [torch.minimum(c - torch.floor(c), torch.ceil(c) - c) for c in coords]
+
+
+def _corners(D):
+    return [[(corner >> axis) & 1 for axis in range(D)] for corner in range(1 << D)]
+
+
+def cell_taps(a, coords, codes, consts):
+    """ (floor per axis, the 2^D taps of the cell every coordinate lies in, in grid_sample's corner order) """
+    D = a.dim() - 1
+    fl = [torch.floor(c) for c in coords]
+    i0 = [f.to(torch.long) for f in fl]
+    return fl, [tap(a, [i0[axis] + bits[axis] for axis in range(D)], codes, consts)[0] for bits in _corners(D)]
+
+
+def multilinear(taps, fr):
+    """ grid_sample's weighted sum for given taps and fractions (fractions outside [0, 1] extend the cell's own polynomial) """
+    D = len(fr)
+    out = torch.zeros_like(taps[0])
+    for t, bits in zip(taps, _corners(D)):
+        w = torch.ones_like(taps[0])
+        for axis in range(D):
+            w = w * (fr[axis] if bits[axis] else (1 - fr[axis]))
+        out = out + t * w
+    return out
+
+
+def abs_rule(consts):
+    return [(abs(float(lo)), abs(float(hi))) for lo, hi in consts]
+
+
+def grid_sample_scale(a, coords, codes, consts):
+    """ S = sum_k w_k |t_k|: the same lookup applied to |a| with |constants| """
+    return grid_sample(a.abs(), coords, codes, abs_rule(consts))
+
+
+def _shifts(D):
+    import itertools
+    return [s for s in itertools.product((-1, 0, 1), repeat=D) if any(s)]
+
+
+def grid_sample_envelope(a, coords, codes, consts, delta):
+    """ E = max over sigma in {-1, 0, 1}^D of |grid_sample(c + sigma * delta) - grid_sample(c)| per sample. A shift that keeps every sample in its cell
+    is evaluated from the cell's taps (gathered once); one that moves some sample across an integer goes through grid_sample itself. """
+    D = len(coords)
+    fl, taps = cell_taps(a, coords, codes, consts)
+    base = multilinear(taps, [c - f for c, f in zip(coords, fl)])
+    env = torch.zeros_like(base)
+    for sig in _shifts(D):
+        pc = [coords[ax] + sig[ax] * delta[ax] for ax in range(D)]
+        crossed = any(bool((torch.floor(pc[ax]) != fl[ax]).any()) for ax in range(D) if sig[ax])
+        val = grid_sample(a, pc, codes, consts) if crossed else multilinear(taps, [p - f for p, f in zip(pc, fl)])
+        env = torch.maximum(env, (val - base).abs())
+    return env
+
+
+def lerp_difference_scale(a, coords, codes, consts):
+    """ G = sum over the levels of nested lerps (last axis first, the order of advect_common.hpp lerp_cell) and over the tap pairs of a level of
+    w_rest * f * |hi - lo|: what a relative perturbation of every pair's fraction, each with its own sign, can move the result by """
+    import itertools
+    D = len(coords)
+    fl, taps = cell_taps(a, coords, codes, consts)
+    fr = [c - f for c, f in zip(coords, fl)]
+    cur = {tuple(bits): t for bits, t in zip(_corners(D), taps)}
+    total = torch.zeros_like(taps[0])
+    for axis in reversed(range(D)):
+        nxt = {}
+        for bits in itertools.product((0, 1), repeat=axis):
+            lo, hi = cur[bits + (0,)], cur[bits + (1,)]
+            w = torch.ones_like(total)
+            for ax in range(axis):
+                w = w * (fr[ax] if bits[ax] else (1 - fr[ax]))
+            total = total + w * fr[axis] * (hi - lo).abs()
+            nxt[bits] = lo + fr[axis] * (hi - lo)
+        cur = nxt
+    return total
+
+
+def limit_windows_cells(a, base, below, above, codes, consts, delta):
+    """ limit_windows for a coordinate given in parts: `base` = the cell (integer-valued) per axis, `below` / `above` = the distances of the point from the cell's
+    lower / upper end, computed from the DISPLACEMENT (an absolute float64 coordinate on an axis of n cells cannot place a point that is 1e-14 cells from a
+    sample). A sample admits the neighbouring cell on an axis where that distance is <= delta. """
+    D = len(base)
+    mid = [b + 0.5 for b in base]
+    lo, hi, _ = closest_limits(a, mid, codes, consts)
+    windows, multi = [(lo, hi)], torch.zeros(lo.shape, dtype=torch.bool)
+    near = [(below[ax] <= delta[ax], above[ax] <= delta[ax]) for ax in range(D)]
+    for sig in _shifts(D):
+        moved = torch.zeros(lo.shape, dtype=torch.bool)
+        pc = []
+        for ax in range(D):
+            m = near[ax][0] if sig[ax] < 0 else (near[ax][1] if sig[ax] > 0 else None)
+            pc.append(mid[ax] if m is None else mid[ax] + sig[ax] * m.to(mid[ax].dtype))
+            if m is not None:
+                moved = moved | m
+        if bool(moved.any()):
+            lo2, hi2, _ = closest_limits(a, pc, codes, consts)
+            windows.append((lo2, hi2))
+            multi = multi | moved
+    return windows, multi
+
+
 # ---- pin and VJP -------------------------------------------------------------------------------------------------------------------------------------------------
 def pin(out, oracle_out, what):
     """ the restatement is trusted through this: its float64 forward equals the oracle's float64 forward to 1e-12 of the largest element """

@@ -16,6 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))   # this file lives there: test infrastructure (it drives the oracle)
 import adjoint_cases as ac           # noqa: E402
+import advect_forward_cases as afc   # noqa: E402
 import diffuse_coef_elementwise_cases as dce   # noqa: E402
 import multigrid_elementwise_cases as mgc   # noqa: E402
 import parity_cases as pc            # noqa: E402
@@ -127,6 +128,14 @@ def main():
                 ac.check_advect_staggered(ctx, mem, res, bc, edt, batch, adt, seed=seed, k0=int(r.integers(-1, 1)), slab_axis=int(r.integers(0, D)))
                 step = f"adjoint elementwise centred {edt.__name__}"
                 ac.check_advect_centered(ctx, mem, res, bc, edt, batch, adt, seed=seed, k0=int(r.integers(-1, 1)), slab_axis=int(r.integers(0, D)), flip=bool(r.integers(0, 2)))
+            # the forward passes element by element under the per-sample bound of tests/advect_forward_cases.py, on every path, in BOTH element types: the
+            # checks build their own fields and wall values on the case's grid and boundary mix
+            fst = float(r.uniform(0.3, 1))
+            for edt in (np.float32, np.float64):
+                for entry in afc.ENTRIES:
+                    step = f"advect forward elementwise {entry} {edt.__name__}"
+                    afc.check_entry(ctx, mem, entry, res, bc, edt, batch, adt, "random", seed=seed, strength=fst)
+            del afc.RECORDS[:]
             # one multigrid V-cycle element by element against the float64 restatement of its recipe (tests/multigrid_ref.py) in fp64, whatever the case's
             # element type: this case's grid and walls, random cell sizes, a random solid sphere more often than not (a PERIODIC axis of one cell is outside
             # what the reference restates)

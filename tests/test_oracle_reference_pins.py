@@ -265,3 +265,37 @@ def test_assembled_csr_operator_equals_the_matrix_free_stencil():
     x1, i1 = O.cg(lambda q: O.masked_laplace(q, dom, None, None), y, np.zeros_like(y), 1e-10, 0, 500)
     x2, i2 = O.cg(lambda q: (A @ q.ravel()).reshape(q.shape), y, np.zeros_like(y), 1e-10, 0, 500)
     assert int(i1.iterations[0]) == int(i2.iterations[0]) and np.abs(x1 - x2).max() <= 1e-9 * np.abs(x1).max()
+
+
+def test_hand_derived_maccormack_limiter_table():
+    """ the oracle's semi-Lagrangian lookups, limiter window and MacCormack result against the literals of tests/limiter_table.py, worked out by hand
+    from phi/physics/advect.py:198-214 and phi/field/_field.py:409-429 (the window in the CELL frame for a staggered component too) """
+    import limiter_table as T
+    row = lambda x: np.asarray(x, np.float64).reshape(1, 1, -1)
+    for dtype in (np.float64, np.float32):
+        # centred
+        dom = O.Domain(T.RES, (0, 0), T.RES, ((PER, PER), (OPN, OPN)))
+        codes, consts = ((PER, PER), (CLO, OPN)), [(0.0, 0.0), T.CEN_CONSTS]
+        v = [np.zeros((1,) + dom.comp_shape(0), dtype), row(T.CEN_FACES).astype(dtype)]
+        s = row(T.CEN_S).astype(dtype)
+        fwd = O.semi_lagrangian_centered(s, v, T.DT, dom, codes, consts)
+        assert np.array_equal(fwd, row(T.CEN_FWD))
+        assert np.array_equal(O.semi_lagrangian_centered(fwd, v, -T.DT, dom, codes, consts), row(T.CEN_BWD))
+        lo, hi = O.closest_limits(s, [np.zeros((1, 1, 8), dtype), row(T.CEN_BACK).astype(dtype)], codes, consts)
+        assert np.array_equal(lo, row(T.CEN_LO)) and np.array_equal(hi, row(T.CEN_HI))
+        assert np.array_equal(np.clip(row(T.CEN_NEW), lo, hi), row(T.CEN_OUT))
+        assert np.array_equal(O.mac_cormack_centered(s, v, T.DT, dom, codes, consts, 1.0), row(T.CEN_OUT))
+        # staggered
+        bcv = np.zeros((2, 2, 2))
+        bcv[1][0][1] = T.STAG_WALL
+        dom = O.Domain(T.RES, (0, 0), T.RES, ((PER, PER), (CLO, OPN)), bcv)
+        zero = np.zeros((1,) + dom.comp_shape(0), dtype)
+        v, g = [zero, row(T.STAG_W).astype(dtype)], [zero, row(T.STAG_G).astype(dtype)]
+        fwd = O.semi_lagrangian_staggered(g, v, T.DT, dom)
+        assert np.array_equal(fwd[1], row(T.STAG_FWD)) and not fwd[0].any()
+        assert np.array_equal(O.semi_lagrangian_staggered(fwd, v, -T.DT, dom)[1], row(T.STAG_BWD))
+        lo, hi = O.closest_limits(g[1], [np.zeros((1, 1, 8), dtype), row(T.STAG_LIMIT_COORD).astype(dtype)], ((PER, PER), (CLO, OPN)), [(0.0, 0.0), (T.STAG_WALL, 0.0)])
+        assert np.array_equal(lo, row(T.STAG_LO)) and np.array_equal(hi, row(T.STAG_HI))
+        assert np.array_equal(np.clip(row(T.STAG_NEW), lo, hi), row(T.STAG_OUT))
+        out = O.mac_cormack_staggered(g, v, T.DT, dom, 1.0)
+        assert np.array_equal(out[1], row(T.STAG_OUT)) and not out[0].any()
