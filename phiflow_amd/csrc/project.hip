@@ -146,16 +146,18 @@ __global__ __launch_bounds__(kBlock) void divergence_kernel(VelGrid g, CComp3<T>
     if (inside && p0 < p1) {
         T lo0 = DIM == 3 ? face0(p0) : T(0);
         for (int p = p0; p < p1; ++p) {
+            // explicit fma chain, the same in divergence_vec_kernel: left to the compiler's contraction the two kernels fused different pairs
+            // (2-D fp32: results that differ in the last bit with the alignment of the caller's buffers)
             T sum = T(0);
             if (DIM == 3) {
                 const T hi0 = face0(p + 1);
-                sum += (hi0 - lo0) * r0;
+                sum = (hi0 - lo0) * r0;
                 lo0 = hi0;
             }
             const T a = c1f[0] ? k1[0] : C1[(long long)p * ps1 + o1[0]], bb = c1f[1] ? k1[1] : C1[(long long)p * ps1 + o1[1]];
-            sum += (bb - a) * r1;
+            sum = fma(bb - a, r1, sum);
             const T c = c2f[0] ? k2[0] : C2[(long long)p * ps2 + o2[0]], d = c2f[1] ? k2[1] : C2[(long long)p * ps2 + o2[1]];
-            sum += (d - c) * r2;
+            sum = fma(d - c, r2, sum);
             const long long cell = ((long long)p * n1 + i1) * n2 + i2;
             T act = T(1);
             if (F) {
@@ -272,10 +274,10 @@ __global__ __launch_bounds__(kBlock) void divergence_vec_kernel(VelGrid g, CComp
             for (int e = 0; e < V; ++e) {
                 const T c = off2 ? (e > 0 ? m.v[e > 0 ? e - 1 : 0] : edge) : m.v[e];
                 const T d = off2 ? m.v[e] : (e < V - 1 ? m.v[e < V - 1 ? e + 1 : e] : edge);
-                T sum = T(0);
-                if (DIM == 3) sum += (hi0.v[e] - lo0.v[e]) * r0;
-                sum += (bb.v[e] - a.v[e]) * r1;
-                sum += (d - c) * r2;
+                T sum = T(0);      // (the fma chain of divergence_kernel: the same bits from either kernel)
+                if (DIM == 3) sum = (hi0.v[e] - lo0.v[e]) * r0;
+                sum = fma(bb.v[e] - a.v[e], r1, sum);
+                sum = fma(d - c, r2, sum);
                 T act = T(1);
                 if (F) {
                     const unsigned f = fl.v[e];
@@ -1005,13 +1007,16 @@ __device__ __forceinline__ double obstacle_sdf(const ObstacleSet& s, int k, cons
 // Bounding boxes of the obstacles of one launch in LDS (half extents, the bounding radius for a rotated box, unbounded along embedded
 // axes), built once per workgroup: the per-patch "is this obstacle anywhere near" test then reads LDS instead of walking the by-value
 // obstacle table in the kernel arguments (dependent scalar loads, ~0.2 us each, per obstacle and patch made these kernels latency-bound).
-__device__ __forceinline__ void obstacle_boxes(const ObstacleSet& s, int ax0, double (*box)[6]) {
+// `margin`: the distance obstacles_near will grow the boxes by. The signed distance of a box is the L-infinity one (obstacle_sdf), so the samples within
+// `margin` of a ROTATED box fill the box grown by `margin` along each of its own axes: its corners lie |half + margin| from the centre, farther than
+// |half| + margin -- the bounding radius stored here is |half + margin| - margin, so that the later `+ margin` reaches them (lies_inside: margin 0).
+__device__ __forceinline__ void obstacle_boxes(const ObstacleSet& s, int ax0, double (*box)[6], double margin) {
     const int k = threadIdx.x;
     if (k < s.count) {
         double rad = 0;
         if (s.rotated[k]) {
-            for (int a = ax0; a < 3; ++a) rad += s.half[k][a] * s.half[k][a];
-            rad = sqrt(rad);
+            for (int a = ax0; a < 3; ++a) rad += (s.half[k][a] + margin) * (s.half[k][a] + margin);
+            rad = sqrt(rad) - margin;
         }
         for (int a = 0; a < 3; ++a) {
             const bool skip = a < ax0 || ((s.skip[k] >> a) & 1);
@@ -1058,10 +1063,10 @@ static void patch_box_slot(const GridView& v, const ObstacleSet& set, int ca, do
         for (int k = 0; k < set.count; ++k) {
             if ((set.skip[k] >> a) & 1) { lo = -1e300; hi = 1e300; break; }
             double h = set.kind[k] == PHIHIP_OBSTACLE_SPHERE ? set.half[k][v.ax0] : set.half[k][a];
-            if (set.rotated[k]) {
+            if (set.rotated[k]) {      // (the box grown by `margin` along its own axes: obstacle_boxes)
                 double r2 = 0;
-                for (int c = v.ax0; c < 3; ++c) r2 += set.half[k][c] * set.half[k][c];
-                h = sqrt(r2);
+                for (int c = v.ax0; c < 3; ++c) r2 += (set.half[k][c] + margin) * (set.half[k][c] + margin);
+                h = sqrt(r2) - margin;
             }
             lo = fmin(lo, set.center[k][a] - h);
             hi = fmax(hi, set.center[k][a] + h);
@@ -1103,7 +1108,7 @@ __global__ __launch_bounds__(kBlock) void obstacle_accessible_kernel(VelGrid g, 
                                                                      PatchBox pb, uint8_t* accessible) {
     const double lower[3] = {lower0, lower1, lower2};
     __shared__ double box[kObstaclesPerLaunch][6];
-    obstacle_boxes(s, g.ax0, box);
+    obstacle_boxes(s, g.ax0, box, 0.0);
     const int tx = threadIdx.x & (kPatchCols - 1), ty = threadIdx.x / kPatchCols;
     const int npatch = pb.first[3];
     for (int patch = blockIdx.x; patch < npatch; patch += gridDim.x) {
@@ -1161,7 +1166,7 @@ __global__ __launch_bounds__(kBlock) void apply_obstacles_kernel(VelGrid g, doub
     for (int a = g.ax0; a < 3; ++a) r2 += 0.25 * g.dx[a] * g.dx[a];
     const double radius = sqrt(r2);
     __shared__ double box[kObstaclesPerLaunch][6];
-    obstacle_boxes(s, g.ax0, box);
+    obstacle_boxes(s, g.ax0, box, radius * 1.000001);
     const int tx = threadIdx.x & (kPatchCols - 1), ty = threadIdx.x / kPatchCols;
     const int npatch = pb.first[3];
     for (int patch = blockIdx.x; patch < npatch; patch += gridDim.x) {

@@ -20,6 +20,7 @@ import advect_forward_cases as afc   # noqa: E402
 import diffuse_coef_elementwise_cases as dce   # noqa: E402
 import multigrid_elementwise_cases as mgc   # noqa: E402
 import parity_cases as pc            # noqa: E402
+import project_elementwise_cases as pec   # noqa: E402
 from phiflow_amd import _capi as C   # noqa: E402
 
 
@@ -148,6 +149,23 @@ def main():
             # (tests/diffuse_coef_ref.py) in fp64, whatever the case's element type: this case's grid and scalar walls, a refresh on the second iteration
             step = "diffuse coef trajectory elementwise"
             dce.check_cg_trajectory_random(ctx, mem, res, s_codes, seed)
+            # the projection stencils and the obstacle kernels element by element under the per-sample bound of tests/project_elementwise_cases.py, in BOTH
+            # element types: the checks build their own fields on the case's grid and boundary mix, with every wall constant non-zero (the normal ones included)
+            mode = pec.MODES[int(r.integers(0, 3))]
+            for edt in (np.float32, np.float64):
+                for kind in ("random", "graded"):
+                    step = f"project elementwise divergence {edt.__name__}"
+                    pec.check_divergence(ctx, mem, res, bc, edt, batch, kind, "none", seed)
+                    pec.check_divergence(ctx, mem, res, bc, edt, batch, kind, mode, seed)
+                    step = f"project elementwise grad_subtract {edt.__name__}"; pec.check_grad_subtract(ctx, mem, res, bc, edt, batch, kind, mode, seed)
+                    step = f"project elementwise laplace {edt.__name__}"; pec.check_laplace(ctx, mem, res, bc, edt, batch, kind, mode, seed)
+                step = f"project elementwise resample {edt.__name__}"; pec.check_centered_to_staggered(ctx, mem, res, bc, edt, batch, "random", seed, rotations=(seed % 4,))
+                step = f"project elementwise diffuse {edt.__name__}"; pec.check_diffuse_explicit(ctx, mem, res, bc, edt, batch, "random", seed)
+                step = f"project elementwise obstacles {edt.__name__}"
+                pdx = pec.make_inputs(res, bc, edt, batch).dx
+                for name in ("rotated box", "sphere", "union of three"):
+                    pec.check_obstacles(ctx, mem, res, bc, edt, batch, pec.pick_scene(name, res, bc, pdx, seed), "random", seed, what=name)
+            del pec.RECORDS[:]
             print("ok  ", tag, flush=True)
         except Exception as e:   # noqa: BLE001 -- report and go on
             fails += 1
