@@ -408,7 +408,7 @@ int phihip_set_deferred_x_update(phihip_ctx* ctx, int enable);
  *                 fraction, and probes the cheaper form every 64 calls. The choice depends on the data only, not on timing.
  *    0            the one-launch-per-component gather kernels for every call
  *    1 / 2        fixed reach (the staggered MacCormack correction has reach 1 only)
- *    3            experimental: reach 1 with 16-row tiles for the self-advection (3-D) */
+ * Any other value is PHIHIP_ERR_BAD_ARG and leaves the setting as it is. */
 int phihip_set_advect_halo(phihip_ctx* ctx, int halo);
 /* The other advection passes -- the correction pass of mac_cormack(v, v), semi_lagrangian / mac_cormack of a centred scalar -- are served from
  * LDS windows too (advect_win.hip; halo 1, gather fix-up for larger displacements) whenever halo != 0, on 3-D grids. On 2-D grids the gather
@@ -424,8 +424,9 @@ int phihip_set_advect_dma(phihip_ctx* ctx, int enable, int32_t* last_was_dma);
 /* r6: placement of the CG workspace. What an iteration of Solve('CG') (phi/physics/fluid.py:156-161) costs on vectors beyond the caches depends on WHICH
  * allocations hold r, d0, d1 -- the relative position of the streams in the physical address space: 512^3 fp32 0.666 ... 0.731 ms per iteration between six
  * workspaces alive at once, every one stable to 0.1 % (profiles/r06_ws_placement_probe.jsonl). The first solve on a freshly grown workspace therefore allocates
- * `candidates` triples, times the iteration loop with the tuned launch plans on each and keeps the fastest (behind the first-call autotune and under its
- * conditions: autotune on, stream not capturing; never more than half of the free device memory; the others are freed before the call returns). Results are
+ * `candidates` triples, times the iteration loop with the launch plans that solve runs (tuned, pinned or analytic) on each and keeps the fastest (behind
+ * the first-call autotune but not under its switch: whenever the stream is not capturing, autotune on or off; never more than half of the free device memory;
+ * the others are freed before the call returns). Results are
  * bit-identical whichever is kept. Vectors of <= 72 MB (256^3 fp32: the Infinity Cache regime) cost the same wherever they live and are not placed;
  * candidates held at once stay within 32 GiB. candidates: 2 ... 16, 0 / 1 = keep the first allocation, < 0 = leave as it is (default 12; environment
  * PHIHIP_WS_CANDIDATES at context creation). *last_candidates (may be NULL) = triples the most recent choice had (0: none yet), last_us (may be NULL) =

@@ -169,11 +169,10 @@ class Library:
         d.phihip_advect_staggered.argtypes = [c_void_p, POINTER(Grid), POINTER(_Ptr3), POINTER(_Ptr3), POINTER(_Ptr3), c_double, c_void_p]
         d.phihip_advect_centered.argtypes = [c_void_p, POINTER(Grid), c_void_p, POINTER((c_int32 * 2) * 3), POINTER((c_double * 2) * 3),
                                              POINTER(_Ptr3), c_void_p, c_double, c_void_p]
-        if hasattr(d, "phihip_grid_sample"):
-            d.phihip_grid_sample.argtypes = [c_void_p, POINTER(Grid), c_void_p, c_int, POINTER(_Ptr3), ctypes.c_int64, c_void_p, c_void_p, c_void_p,
-                                             c_void_p]
-            d.phihip_grid_sample_backward.argtypes = [c_void_p, POINTER(Grid), c_void_p, c_int, POINTER(_Ptr3), ctypes.c_int64, c_void_p, c_void_p,
-                                                      POINTER(_Ptr3), c_void_p]
+        d.phihip_grid_sample.argtypes = [c_void_p, POINTER(Grid), c_void_p, c_int, POINTER(_Ptr3), ctypes.c_int64, c_void_p, c_void_p, c_void_p,
+                                         c_void_p]
+        d.phihip_grid_sample_backward.argtypes = [c_void_p, POINTER(Grid), c_void_p, c_int, POINTER(_Ptr3), ctypes.c_int64, c_void_p, c_void_p,
+                                                  POINTER(_Ptr3), c_void_p]
         d.phihip_mac_cormack_staggered.argtypes = [c_void_p, POINTER(Grid), POINTER(_Ptr3), POINTER(_Ptr3), POINTER(_Ptr3), c_double, c_double,
                                                    c_void_p]
         d.phihip_mac_cormack_centered.argtypes = [c_void_p, POINTER(Grid), c_void_p, POINTER((c_int32 * 2) * 3), POINTER((c_double * 2) * 3),
@@ -230,16 +229,14 @@ class Library:
         d.phihip_set_tuning.argtypes = [c_void_p, c_int, c_int, c_int]
         d.phihip_set_tuning_kernel.argtypes = [c_void_p, c_int, c_int, c_int, c_int]
         d.phihip_set_small_grid_solver.argtypes = [c_void_p, c_int]
-        if hasattr(d, "phihip_set_deferred_x_update"):
-            d.phihip_set_deferred_x_update.argtypes = [c_void_p, c_int]
+        d.phihip_set_deferred_x_update.argtypes = [c_void_p, c_int]
         d.phihip_set_advect_halo.argtypes = [c_void_p, c_int]
         d.phihip_set_advect_chunk.argtypes = [c_void_p, c_int]
         d.phihip_set_advect_windows_2d.argtypes = [c_void_p, c_int]
         d.phihip_query_advect_chunk.argtypes = [c_void_p, POINTER(c_int32)]
         d.phihip_workspace_placement.argtypes = [c_void_p, c_int, POINTER(c_int32), POINTER(c_double)]
         d.phihip_set_autotune.argtypes = [c_void_p, c_int]
-        if hasattr(d, 'phihip_set_advect_dma'):
-            d.phihip_set_advect_dma.argtypes = [c_void_p, c_int, POINTER(c_int32)]
+        d.phihip_set_advect_dma.argtypes = [c_void_p, c_int, POINTER(c_int32)]
         d.phihip_set_single_reduction_cg.argtypes = [c_void_p, c_int, ctypes.c_longlong]
         d.phihip_set_resident_cg.argtypes = [c_void_p, c_int, ctypes.c_longlong]
         d.phihip_allreduce_residual.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]
@@ -624,8 +621,9 @@ class Context:
         self.lib.check(self.lib.dll.phihip_set_small_grid_solver(self.handle, int(enable)))
 
     def set_deferred_x_update(self, enable: bool):
-        if hasattr(self.lib.dll, "phihip_set_deferred_x_update"):
-            self.lib.check(self.lib.dll.phihip_set_deferred_x_update(self.handle, int(bool(enable))))
+        fn = self.lib.dll.phihip_set_deferred_x_update
+        if callable(fn):                            # (a no-op on the stand-in of a strict=False library that lacks the symbol)
+            self.lib.check(fn(self.handle, int(bool(enable))))
 
     def workspace_placement(self, candidates: int = -1) -> dict:
         """ Candidate allocations of the CG workspace the first solve on a freshly grown workspace chooses from (include/phihip.h phihip_workspace_placement):

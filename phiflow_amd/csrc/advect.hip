@@ -155,7 +155,7 @@ static int check_advect_sizes(const GridView& v) {
     return PHIHIP_OK;
 }
 
-// reach of an LDS-staged pass of `kind`: the user's fixed setting (phihip_set_advect_halo 0 / 1 / 2 / 3), or the adaptive choice (-1, default)
+// reach of an LDS-staged pass of `kind`: the user's fixed setting (phihip_set_advect_halo 0 / 1 / 2), or the adaptive choice (-1, default)
 static long long grid_fingerprint(const GridView& v) {
     unsigned long long h = 1469598103934665603ULL;      // FNV-1a in unsigned arithmetic (wraps by definition)
     const long long parts[6] = {v.n[0], v.n[1], v.n[2], v.batch, v.dtype, v.rank};
@@ -164,8 +164,7 @@ static long long grid_fingerprint(const GridView& v) {
 }
 static int pass_reach(phihip_ctx* ctx, const GridView& v, int kind, bool has_wide, hipStream_t s) {
     const int reach = ctx->adv_halo >= 0 ? ((!has_wide && ctx->adv_halo > 1) ? 1 : ctx->adv_halo) : adv_choose(ctx, kind, has_wide, grid_fingerprint(v), s);
-    ctx->adv_reach_now = reach >= 2 ? 2 : (reach == 1 ? 1 : 0);       // (3 = the experimental 16-row tile: reach 1... tagged 1 below)
-    if (reach == 3) ctx->adv_reach_now = 1;
+    ctx->adv_reach_now = reach >= 2 ? 2 : (reach == 1 ? 1 : 0);
     return reach;
 }
 static int pass_done(phihip_ctx* ctx, int kind, int reach, hipStream_t s) {

@@ -949,14 +949,7 @@ static int launch_win_off(phihip_ctx* ctx, const GridView& v, const VelGrid& g, 
             constexpr int V = 16 / (int)sizeof(T);
             bool regular = !consts && ctx->adv_dma != 0 && !v.unaligned && v.bc[2][0] == PHIHIP_BC_PERIODIC;
             for (int c = 0; c < 3; ++c) regular = regular && g.cn[c][2] % V == 0 && ((size_t)call.vel[c] % 16 == 0) && ((size_t)call.fwd[c] % 16 == 0);
-            if (regular) {
-                // (experiment switch PHIHIP_WIN_DMA_ROWS=4: 4-row tiles -- 47 KB of LDS, three workgroups per CU instead of two at 100 VGPRs)
-                static const int rows = [] { const char* e = getenv("PHIHIP_WIN_DMA_ROWS"); return e && e[0] == '4' ? 4 : 8; }();
-                if constexpr (sizeof(T) == 4 && T1 == 8) {
-                    if (rows == 4) return launch_win_inst<T, KIND, DIM, 4, OFFM, false, H, true>(ctx, v, g, call, s);
-                }
-                return launch_win_inst<T, KIND, DIM, T1, OFFM, false, H, true>(ctx, v, g, call, s);
-            }
+            if (regular) return launch_win_inst<T, KIND, DIM, T1, OFFM, false, H, true>(ctx, v, g, call, s);
         }
         if (!consts) return launch_win_inst<T, KIND, DIM, T1, OFFM, false, H>(ctx, v, g, call, s);
     }

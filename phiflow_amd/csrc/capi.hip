@@ -1171,7 +1171,7 @@ int phihip_set_small_grid_solver(phihip_ctx* ctx, int enable) {
 
 int phihip_set_advect_halo(phihip_ctx* ctx, int halo) {
     PHIHIP_REQUIRE(ctx != nullptr, "ctx is NULL");
-    PHIHIP_REQUIRE(halo >= -1 && halo <= 3, "advect halo must be -1 (adaptive), 0 (gather kernels), 1, 2 or 3 (experimental: halo 1 with 16-row tiles, 3-D only)");
+    PHIHIP_REQUIRE(halo >= -1 && halo <= 2, "advect halo must be -1 (adaptive), 0 (gather kernels), 1 or 2 (got %d)", halo);
     ctx->adv_halo = halo;
     for (auto& K : ctx->adv_policy)
         for (auto& P : K.e) { P.mode = 1; P.calls = 0; P.pending = false; }

@@ -518,9 +518,8 @@ static int autotune_cg(phihip_ctx* ctx, const GridView& v, const uint8_t* flags,
     static const int kChunks[12] = {128, 96, 64, 48, 32, 24, 16, 12, 8, 4, 2, 1};
     struct Cand { int id, chunk; float us; };
     const size_t vec_bytes = (size_t)v.batch * v.cells * sizeof(T);
-    // r6: the candidates move the caller's right-hand side, not zeros (alpha = beta = 0 keep r = d = rhs and x as it is). PHIHIP_AUTOTUNE_DATA=0: zeros as until r5
-    static const bool kRealData = [] { const char* e = getenv("PHIHIP_AUTOTUNE_DATA"); return !(e && e[0] == '0'); }();
-    if (kRealData && rhs) {
+    // r6: the candidates move the caller's right-hand side, not zeros (alpha = beta = 0 keep r = d = rhs and x as it is); zeros only where there is none
+    if (rhs) {
         PHIHIP_CHECK_HIP(hipMemcpyAsync(r, rhs, vec_bytes, hipMemcpyDeviceToDevice, s));
         PHIHIP_CHECK_HIP(hipMemcpyAsync(d0, rhs, vec_bytes, hipMemcpyDeviceToDevice, s));
         PHIHIP_CHECK_HIP(hipMemcpyAsync(d1, rhs, vec_bytes, hipMemcpyDeviceToDevice, s));

@@ -213,7 +213,7 @@ struct phihip_ctx {
     int adv_last_chunk = 0;       // planes per workgroup the most recent tiled self-advection ran with (phihip_query_advect_chunk)
     int adv_halo = -1;            // phihip_set_advect_halo: reach of the LDS-staged advection kernels. -1 (default) = adaptive per kind of pass (AdvPolicy below),
                                   // 0 = the gather kernels of advect.hip, 1 / 2 = fixed (3 = experimental 16-row tiles of the self-advection)
-    bool adv_win_2d = false;      // advect_win.hip on 2-D grids (slower than the gather kernels there; phihip_set_advect_halo(ctx, 4) switches it on for the parity tests)
+    bool adv_win_2d = false;      // advect_win.hip on 2-D grids (slower than the gather kernels there; phihip_set_advect_windows_2d switches it on for the parity tests)
     // first-call autotune of the CG marching kernels: the candidates of the plan model are timed once per (grid, family) on the
     // context's own workspace and the fastest is cached here. PHIHIP_AUTOTUNE=0 in the environment / phihip_set_autotune(ctx, 0)
     // keep the analytic plan (bit-reproducible launch geometry across processes).

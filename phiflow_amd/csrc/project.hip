@@ -18,8 +18,7 @@ template <typename T>
 struct CComp3 {
     const T* p[3];
 };
-// V elements at 16-byte alignment: 16 bytes (fp32 V = 4, fp64 V = 2) or 32 bytes (fp64 V = 4: two dwordx4 -- r4: with V = 2 the fp64
-// instantiations of the vector kernels below issue one address per 16 bytes and are bound by the address units, not by HBM)
+// V elements at 16-byte alignment: one dwordx4 per lane (fp32 V = 4, fp64 V = 2)
 template <typename T, int V>
 struct alignas(16) VecA {
     T v[V];
@@ -35,16 +34,10 @@ __device__ __forceinline__ VecA<T, V> veca_zero() {
     for (int i = 0; i < V; ++i) r.v[i] = T(0);
     return r;
 }
-// cells per thread of the vector kernels: 16 bytes (fp32 4, fp64 2). The 32-byte fp64 form (4 cells: two dwordx4 per lane at a lane stride
-// of 32 bytes, so each instruction touches every other 16 bytes of its lines) was the default for a few commits of r4 and LOST on the same
-// box against the 16-byte form: 384^3 fp64 closed gradient subtraction 0.64 -> 0.885 ms, divergence 0.384 -> 0.432, resample 0.56 -> 0.78
-// (profiles/r04_time_frow_session_h.jsonl). It stays instantiated behind PHIHIP_F64_VEC_CELLS=4 for A/B runs only.
-static inline int f64_vec_cells_setting() {
-    static const int v = [] { const char* e = getenv("PHIHIP_F64_VEC_CELLS"); return (e && e[0] == '4') ? 4 : 2; }();
-    return v;
-}
+// cells per thread of the vector kernels: 16 bytes. (32-byte fp64 lanes -- two dwordx4 per lane -- lost against this on the same box:
+// 384^3 fp64 closed gradient subtraction 0.64 -> 0.885 ms, profiles/r04_time_frow_session_h.jsonl.)
 template <typename T>
-static inline int vec_cells(int n2) { return sizeof(T) == 4 ? 4 : ((f64_vec_cells_setting() == 4 && n2 % 4 == 0) ? 4 : 2); }
+constexpr int kVecCells = 16 / sizeof(T);
 // V elements at ELEMENT alignment (rows of n2 - 1 / n2 + 1 faces do not start on 16-byte boundaries; gfx950 takes dwordx4 at any 4-byte address)
 template <typename T, int V>
 struct __attribute__((packed, aligned(sizeof(T)))) VecU {
@@ -382,7 +375,7 @@ template <typename T, int DIM>
 static int launch_divergence(phihip_ctx* ctx, const GridView& v, const VelGrid& g, const void* const vel[3], const uint8_t* flags, int fpb, void* div,
                              int finite_guard, int* nblk_out, hipStream_t s) {
     CComp3<T> c{{(const T*)vel[0], (const T*)vel[1], (const T*)vel[2]}};
-    const int V = vec_cells<T>(v.n[2]);
+    constexpr int V = kVecCells<T>;
     const bool vec = divergence_vec_ok<T>(v, vel, flags, div, V);
     int ltpr = 6;                                                 // threads along a row: 64, fewer on narrow grids (whole workgroup rows instead of idle lanes)
     if (vec) while (ltpr > 0 && (1 << (ltpr - 1)) * V >= v.n[2]) --ltpr;
@@ -399,11 +392,8 @@ static int launch_divergence(phihip_ctx* ctx, const GridView& v, const VelGrid& 
     PHIHIP_TRY(ensure_buffer(ctx->ws_div, (size_t)2 * v.batch * nblk * sizeof(double)));
     double* part_sum = (double*)ctx->ws_div.ptr;
     double* part_act = part_sum + (size_t)v.batch * nblk;
-    if (vec && V == 4)
-        hipLaunchKernelGGL((divergence_vec_kernel<T, DIM, 4>), dim3(nblk, v.batch), dim3(kBlock), 0, s, g, c, flags, fpb, (T*)div, part_sum, part_act, nblk,
-                           tiles1, tiles2, chunk_planes, ltpr, finite_guard);
-    else if (vec)
-        hipLaunchKernelGGL((divergence_vec_kernel<T, DIM, 2>), dim3(nblk, v.batch), dim3(kBlock), 0, s, g, c, flags, fpb, (T*)div, part_sum, part_act, nblk,
+    if (vec)
+        hipLaunchKernelGGL((divergence_vec_kernel<T, DIM, V>), dim3(nblk, v.batch), dim3(kBlock), 0, s, g, c, flags, fpb, (T*)div, part_sum, part_act, nblk,
                            tiles1, tiles2, chunk_planes, ltpr, finite_guard);
     else
         hipLaunchKernelGGL((divergence_kernel<T, DIM>), dim3(nblk, v.batch), dim3(kBlock), 0, s, g, c, flags, fpb, (T*)div, part_sum, part_act, nblk,
@@ -622,7 +612,7 @@ static void launch_grad_subtract(const GridView& v, const VelGrid& g, const uint
     for (int a = 0; a < 3; ++a)
         for (int c = v.ax0; c < 3; ++c) nmax[a] = v.cn[c][a] > nmax[a] ? v.cn[c][a] : nmax[a];
     Comp3<T> c{{(T*)vel[0], (T*)vel[1], (T*)vel[2]}};
-    const int V = vec_cells<T>(v.n[2]);
+    constexpr int V = kVecCells<T>;
     int scalar_comps = 7;
     // vector path: rows of the pressure are whole vectors and the buffers of p, of the flags and of the a0 / a1 components are 16-byte
     // aligned (flags: V bytes); the a2 component only needs element alignment
@@ -634,12 +624,8 @@ static void launch_grad_subtract(const GridView& v, const VelGrid& g, const uint
         const int patches1 = ceil_div(nmax[1], kPatchRows), patches2 = ceil_div(v.n[2], kPatchCols * V);
         const long long npatch = (long long)nmax[0] * patches1 * patches2;
         const int nblk = npatch < 16384 ? (int)npatch : 16384;
-        if (V == 4)
-            hipLaunchKernelGGL((grad_subtract_vec_kernel<T, DIM, 4>), dim3(nblk, v.batch), dim3(kBlock), 0, s, g, c, (const T*)p, flags, fpb, nmax[0], patches1,
-                               patches2, vec_comps);
-        else
-            hipLaunchKernelGGL((grad_subtract_vec_kernel<T, DIM, 2>), dim3(nblk, v.batch), dim3(kBlock), 0, s, g, c, (const T*)p, flags, fpb, nmax[0], patches1,
-                               patches2, vec_comps);
+        hipLaunchKernelGGL((grad_subtract_vec_kernel<T, DIM, V>), dim3(nblk, v.batch), dim3(kBlock), 0, s, g, c, (const T*)p, flags, fpb, nmax[0], patches1,
+                           patches2, vec_comps);
         scalar_comps = 7 & ~vec_comps;
     }
     if (scalar_comps) {
@@ -832,7 +818,7 @@ __global__ __launch_bounds__(kBlock) void centered_to_staggered_vec_kernel(VelGr
 template <typename T, int DIM>
 static bool launch_c2s_vec(const GridView& v, const VelGrid& g, const ScalarBc& sb, const void* sfield, const double vector[3], int accumulate,
                            void* const out[3], hipStream_t s) {
-    const int V = vec_cells<T>(v.n[2]);
+    constexpr int V = kVecCells<T>;
     bool ok = v.n[2] % V == 0 && ((uintptr_t)sfield & 15u) == 0;
     for (int ca = v.ax0; ca < 2; ++ca) ok = ok && ((uintptr_t)out[ca] & 15u) == 0;
     ok = ok && ((uintptr_t)out[2] & (sizeof(T) - 1)) == 0;
@@ -850,12 +836,8 @@ static bool launch_c2s_vec(const GridView& v, const VelGrid& g, const ScalarBc& 
     const long long npatch = (long long)nmax[0] * patches1 * patches2;
     const int nblk = npatch < 16384 ? (int)npatch : 16384;
     Comp3<T> oc{{(T*)out[0], (T*)out[1], (T*)out[2]}};
-    if (V == 4)
-        hipLaunchKernelGGL((centered_to_staggered_vec_kernel<T, DIM, 4>), dim3(nblk, v.batch), dim3(kBlock), 0, s, g, sb, oc, (const T*)sfield, (T)vector[0],
-                           (T)vector[1], (T)vector[2], accumulate, comps, nmax[0], patches1, patches2, ltpr);
-    else
-        hipLaunchKernelGGL((centered_to_staggered_vec_kernel<T, DIM, 2>), dim3(nblk, v.batch), dim3(kBlock), 0, s, g, sb, oc, (const T*)sfield, (T)vector[0],
-                           (T)vector[1], (T)vector[2], accumulate, comps, nmax[0], patches1, patches2, ltpr);
+    hipLaunchKernelGGL((centered_to_staggered_vec_kernel<T, DIM, V>), dim3(nblk, v.batch), dim3(kBlock), 0, s, g, sb, oc, (const T*)sfield, (T)vector[0],
+                       (T)vector[1], (T)vector[2], accumulate, comps, nmax[0], patches1, patches2, ltpr);
     return true;
 }
 

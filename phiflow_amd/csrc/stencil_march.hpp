@@ -390,9 +390,6 @@ constexpr int march_min_waves() {
 // rows, the remaining threads idle. No halo COLUMNS exist: the neighbours beyond a row's ends are read from the row's own LDS copy with
 // the boundary rule (wrap / clamp / zero). Why: the power-of-two tiles cannot span a 288- ... 448-cell row, and their halo columns are what
 // the mid-size dip is made of (1.49 fabric read requests per needed one at 320^3 against 1.13 at 512^3).
-#ifndef PHIHIP_SAWTOOTH
-#define PHIHIP_SAWTOOTH 1
-#endif
 // march_body: the kernel's body as a device function (r6), so that TWO entry points share it -- march_kernel (one lattice per launch: every CG phase) and
 // march_apply_multi_kernel (MODE_APPLY on up to three lattices in ONE launch: the components of diffuse.explicit, phi/physics/diffuse.py:13-60 is one call).
 template <typename T, int V, int R, int TPR, int MODE, bool FLAGS, bool DIM3, bool BIDIR = false, bool UNAL = false, bool ROWT = false>
@@ -441,7 +438,7 @@ __device__ __forceinline__ void march_body(const MarchGrid& g, const MarchArgs<T
     // and UPDATE launches that share two of their three vectors; what one launch touched last is what is still in the L2 / the 256 MiB Infinity Cache when
     // the next one starts, so the next one starts there (tools/micro/mall_sawtooth.hip: a plain triad over rotating vectors gains 3 % at 256^3 / 512^3
     // and 8 ... 15 % at 320^3 ... 384^3).
-    constexpr bool DOWN = PHIHIP_SAWTOOTH && IS_UP && DIM3;
+    constexpr bool DOWN = IS_UP && DIM3;
     bid = DOWN ? xcd_order_rev(bid, g.nblk) : xcd_order(bid, g.nblk);
     const int t2 = bid % g.tiles2;
     const int t1 = (bid / g.tiles2) % g.tiles1;

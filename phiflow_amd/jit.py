@@ -46,8 +46,6 @@ import torch
 
 from .field import Field
 
-import os
-_FUSED_COPY = os.environ.get("PHIHIP_JIT_FUSED_COPY", "0") == "1"      # see JitFunction.__call__: NOT safe in front of a replay on this ROCm build (tools/micro/jit_flaky_probe.py)
 _STATE = threading.local()         # per thread: a capture on one thread must not switch another thread's solves to the no-read-back form
 
 
@@ -254,20 +252,13 @@ class JitFunction:
                 variants.append(cap)
             if cap is None:
                 cap = variants[0]
-                # One copy per tensor, by `copy_`. A fused `torch._foreach_copy_` (one launch, ~3 % faster on the 128^2 plume) is NOT safe in front of a replay on this
-                # ROCm build (PHIHIP_JIT_FUSED_COPY=1 switches it on for experiments). Two separate findings: (i) r5 saw the replay behind a fused launch leave the
-                # eager bits by a rounding-level amount -- r6 removed the library's share of that (which kernel computed a sample of an advection pass was policy and
-                # the paths did not share one arithmetic: csrc/advect_common.hpp; all nine variants of tools/micro/jit_foreach_debug.py then gave the eager bits in a
-                # fresh process, profiles/r06_jit_foreach_debug.txt) and switched the fused copy on; (ii) with it on, a replay on a context that had served other
-                # grids before FAULTED (GPU memory access fault at the first pure replay, tools/micro/jit_flaky_probe.py: every run with the fused copy, no run of
-                # 2 x 24 configurations with per-tensor copies -- profiles/r06_jit_flaky_probe.txt) or, in the test suite, differed from the eager step in the last
-                # bits. A torch-only reproducer was attempted (tools/micro/graph_after_foreach_repro.py). So: per-tensor copies ship.
+                # One copy per tensor, by `copy_`, and it must stay that way: a fused `torch._foreach_copy_` (one launch, ~3 % faster on the 128^2 plume) is NOT safe
+                # in front of a replay on this ROCm build. With it, a replay on a context that had served other grids before FAULTED (GPU memory access fault at the
+                # first pure replay: every run with the fused copy, no run of 2 x 24 configurations with per-tensor copies -- profiles/r06_jit_flaky_probe.txt) or, in
+                # the test suite, differed from the eager step in the last bits.
                 pairs = [(dst, src) for dst, src in zip(cap.inputs, tensors) if dst.data_ptr() != src.data_ptr()]
-                if len(pairs) > 1 and _FUSED_COPY:
-                    torch._foreach_copy_([d for d, _ in pairs], [s for _, s in pairs])
-                else:
-                    for d, s in pairs:
-                        d.copy_(s)
+                for d, s in pairs:
+                    d.copy_(s)
                 self.input_copies += len(pairs)
         cap.graph.replay()
         self.replays += 1

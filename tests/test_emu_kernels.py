@@ -560,6 +560,10 @@ def test_bad_arguments_are_reported(emu_ctx, emu_library):
     with pytest.raises(pc.C.PhiHipError) as e:                    # unknown solve method
         emu_ctx.cg_solve(grid, 0, 1, 8, 16, pc.C.Solve(1e-5, 0.0, 10, 50, 10, 7))
     assert e.value.status == -1 and "method" in str(e.value)
+    with pytest.raises(pc.C.PhiHipError) as e:                    # reach 3 (fp32 16-row tiles) was an experiment and is gone: -1 ... 2 only
+        emu_ctx.set_advect_halo(3)
+    assert e.value.status == -1 and "-1" in str(e.value) and "2" in str(e.value)
+    emu_ctx.set_advect_halo(-1)                                   # the refused call left the adaptive reach as it was, and it can still be set
 
 
 def test_bad_arguments_of_the_widened_entry_points(emu_ctx):
