@@ -184,7 +184,7 @@ int phihip_build_cellflags(phihip_ctx* ctx, const phihip_grid* grid, const uint8
 
 /* ---- f3: obstacles rasterised on the device (phi/physics/fluid.py:130-137, 212-240; phi/geom/_box.py:174-185,217-236;
  *          phi/geom/_sphere.py:107-120; phi/field/_angular_velocity.py:10-47) ------------------------------------------- */
-typedef enum phihip_obstacle_kind { PHIHIP_OBSTACLE_BOX = 0, PHIHIP_OBSTACLE_SPHERE = 1 } phihip_obstacle_kind;
+typedef enum phihip_obstacle_kind { PHIHIP_OBSTACLE_BOX = 0, PHIHIP_OBSTACLE_SPHERE = 1, PHIHIP_OBSTACLE_SDF = 2 /* f13, below */ } phihip_obstacle_kind;
 /* Obstacle(geometry, velocity, angular_velocity) with geometry = Box / Cuboid (center, half_size) or Sphere (center, radius) */
 typedef struct phihip_obstacle {
     int32_t kind;                 /* phihip_obstacle_kind */
@@ -195,7 +195,7 @@ typedef struct phihip_obstacle {
     int32_t embed_mask;           /* bit d set: the geometry is infinitely long along axis d (x = bit 0): that coordinate is ignored
                                    * (phi.geom.embed / infinite_cylinder, phi/geom/_embed.py:62-66,139-158). Such obstacles neither
                                    * rotate nor carry a rotation matrix. */
-    int32_t reserved;
+    int32_t reserved;             /* kind PHIHIP_OBSTACLE_SDF: the slot phihip_sdf_bind returned; otherwise unused */
     double center[3];             /* x, y[, z] */
     double half_size[3];          /* box: half extents; sphere: half_size[0] = radius */
     double velocity[3];           /* linear velocity of the obstacle */
@@ -212,6 +212,37 @@ int phihip_obstacle_accessible(phihip_ctx* ctx, const phihip_grid* grid, const p
  *   v = safe_mul(1 - m, v) + safe_mul(m, (angular_velocity x (x_face - center) + velocity) . e_d)   (second term: moving only) */
 int phihip_apply_obstacles(phihip_ctx* ctx, const phihip_grid* grid, const phihip_obstacle* obstacles, int count,
                            void* const velocity[3], void* stream);
+
+/* ---- f13: obstacles of arbitrary shape from a signed-distance grid (phi.geom.SDFGrid, phi/geom/_sdf_grid.py:13-243) ----------------
+ * The array holds one signed distance per virtual cell of `bounds` (res cells per axis, dense C-contiguous, last axis fast), fp32 or fp64
+ * independent of the velocity's element type. With res the array's resolution and size = upper - lower:
+ *   sdf_val(x) = multilinear(sdf, (x - lower) / size * res - 0.5), every tap index clamped to [0, res - 1]   (:150-151, :184-185;
+ *                math.grid_sample(.., ZERO_GRADIENT) [PHIML-RECALL])
+ *   lies_inside(x)                 approximate_outside: lower <= x <= upper (inclusive) and sdf_val <= 0; else sdf_val <= 0   (:149-156)
+ *   approximate_signed_distance(x) approximate_outside: sdf_val within the bounds, |x - center| - bounding_radius outside; else sdf_val  (:183-191)
+ * A description is BOUND to a slot of the context (PHIHIP_SDF_SLOTS per context); an obstacle of kind PHIHIP_OBSTACLE_SDF names the slot in
+ * `reserved` and carries its linear `velocity` as usual; center / half_size / rotation are ignored. group, embed_mask and angular_velocity
+ * must be 0 (PHIHIP_ERR_UNSUPPORTED: an SDF grid is no member of a union, is not embedded and does not follow a rotation). The array must
+ * stay alive and unchanged while the slot is bound. */
+#define PHIHIP_SDF_SLOTS 64
+typedef struct phihip_sdf_grid {
+    const void* sdf;              /* DEVICE pointer to the values */
+    int32_t dtype;                /* phihip_dtype of the values */
+    int32_t rank;                 /* 2 or 3: must equal the rank of the grids the obstacle meets */
+    int32_t res[3];               /* values per axis x, y[, z] (>= 1) */
+    int32_t approximate_outside;  /* != 0: the reference's default */
+    double lower[3];              /* bounds */
+    double upper[3];
+    double center[3];             /* used outside the bounds only (approximate_outside) */
+    double bounding_radius;
+} phihip_sdf_grid;
+/* copies the description into a free slot of the context and returns its number in *slot */
+int phihip_sdf_bind(phihip_ctx* ctx, const phihip_sdf_grid* desc, int32_t* slot);
+int phihip_sdf_release(phihip_ctx* ctx, int32_t slot);
+/* sample_sdf (phi/geom/_sdf_grid.py:245-298): out[cell] = min over the `count` analytic obstacles (kind BOX / SPHERE; rotation, embed_mask
+ * honoured; group ignored: the list is ONE union) of approximate_signed_distance at the centres of the cells of desc (res, lower, upper,
+ * dtype, rank; desc->sdf is ignored). out: DEVICE array [res...] of desc->dtype. */
+int phihip_sdf_from_analytic(phihip_ctx* ctx, const phihip_sdf_grid* desc, const phihip_obstacle* obstacles, int count, void* out, void* stream);
 
 /* ---- a2/a3: field.divergence (phi/field/_field_math.py:589,617-626) and fluid._balance_divergence (fluid.py:205-209) */
 /* div = divergence(v) [* active]; flags may be NULL. `balance` is a bit set: PHIHIP_DIV_BALANCE additionally subtracts the

@@ -36,6 +36,7 @@ EXPORTED_SYMBOLS = (
     "phihip_precondition_apply", "phihip_set_multigrid", "phihip_query_multigrid",
     "phihip_field_laplace", "phihip_field_laplace_centered", "phihip_gradient_centered", "phihip_gradient_centered_backward",
     "phihip_divergence_centered", "phihip_divergence_centered_backward", "phihip_curl_2d", "phihip_curl_2d_backward",
+    "phihip_sdf_bind", "phihip_sdf_release", "phihip_sdf_from_analytic",
 )
 
 
@@ -64,7 +65,23 @@ class ObstacleStruct(ctypes.Structure):
                 ("velocity", c_double * 3), ("angular_velocity", c_double * 3), ("rotation", c_double * 9)]
 
 
-OBSTACLE_BOX, OBSTACLE_SPHERE = 0, 1
+OBSTACLE_BOX, OBSTACLE_SPHERE, OBSTACLE_SDF = 0, 1, 2
+SDF_SLOTS = 64
+
+
+class SdfGridStruct(ctypes.Structure):
+    """ phihip_sdf_grid """
+    _fields_ = [("sdf", c_void_p), ("dtype", c_int32), ("rank", c_int32), ("res", c_int32 * 3), ("approximate_outside", c_int32), ("lower", c_double * 3),
+                ("upper", c_double * 3), ("center", c_double * 3), ("bounding_radius", c_double)]
+
+
+def make_sdf_grid(ptr: int, dtype: int, res, lower, upper, center, bounding_radius: float, approximate_outside: bool) -> SdfGridStruct:
+    """ values at `ptr` (device, dense, last axis fast) of resolution `res` on the box [lower, upper], all in the order of the grids the obstacle meets """
+    d = SdfGridStruct()
+    d.sdf, d.dtype, d.rank, d.approximate_outside, d.bounding_radius = ptr or None, int(dtype), len(res), int(bool(approximate_outside)), float(bounding_radius)
+    for k in range(len(res)):
+        d.res[k], d.lower[k], d.upper[k], d.center[k] = int(res[k]), float(lower[k]), float(upper[k]), float(center[k])
+    return d
 DIV_BALANCE, DIV_FINITE_GUARD = 1, 4      # bits of the `balance` argument (include/phihip.h PHIHIP_DIV_*)
 
 
@@ -75,9 +92,10 @@ def make_obstacles(items) -> "ctypes.Array":
         arr[k].kind = int(it["kind"])
         arr[k].group = int(it.get("group", 0))
         arr[k].embed_mask = int(it.get("embed_mask", 0))
-        for d, val in enumerate(it["center"]):
+        arr[k].reserved = int(it.get("slot", 0))      # kind OBSTACLE_SDF: the slot of Context.sdf_bind
+        for d, val in enumerate(it.get("center", ())):
             arr[k].center[d] = float(val)
-        for d, val in enumerate(it["half_size"]):
+        for d, val in enumerate(it.get("half_size", ())):
             arr[k].half_size[d] = float(val)
         for d, val in enumerate(it.get("velocity", ())):
             arr[k].velocity[d] = float(val)
@@ -259,6 +277,9 @@ class Library:
         d.phihip_divergence_centered_backward.argtypes = [c_void_p, POINTER(Grid), _bc, c_void_p, c_void_p, c_void_p]
         d.phihip_curl_2d.argtypes = [c_void_p, POINTER(Grid), c_int, c_void_p, c_void_p, _bc, _val, c_void_p, c_void_p]
         d.phihip_curl_2d_backward.argtypes = [c_void_p, POINTER(Grid), c_int, _bc, c_void_p, c_void_p, c_void_p, c_void_p]
+        d.phihip_sdf_bind.argtypes = [c_void_p, POINTER(SdfGridStruct), POINTER(c_int32)]
+        d.phihip_sdf_release.argtypes = [c_void_p, c_int32]
+        d.phihip_sdf_from_analytic.argtypes = [c_void_p, POINTER(SdfGridStruct), POINTER(ObstacleStruct), c_int, c_void_p, c_void_p]
         for name in EXPORTED_SYMBOLS:
             if name not in ("phihip_version", "phihip_last_error", "phihip_build_id"):
                 getattr(d, name).restype = c_int
@@ -460,6 +481,19 @@ class Context:
     def apply_obstacles(self, grid, obstacles, count, velocity, stream=0):
         self.lib.check(self.lib.dll.phihip_apply_obstacles(self.handle, ctypes.byref(grid), obstacles, int(count), ctypes.byref(ptr3(velocity)),
                                                            stream or None))
+
+    def sdf_bind(self, desc: SdfGridStruct) -> int:
+        """ binds a signed-distance grid to a free slot of this context; the array at desc.sdf must outlive the binding """
+        slot = c_int32(-1)
+        self.lib.check(self.lib.dll.phihip_sdf_bind(self.handle, ctypes.byref(desc), ctypes.byref(slot)))
+        return int(slot.value)
+
+    def sdf_release(self, slot: int):
+        self.lib.check(self.lib.dll.phihip_sdf_release(self.handle, int(slot)))
+
+    def sdf_from_analytic(self, desc: SdfGridStruct, obstacles, count, out, stream=0):
+        """ sample_sdf: min over the analytic obstacles of the signed distance at the cell centres of `desc` -> out (device, desc.dtype) """
+        self.lib.check(self.lib.dll.phihip_sdf_from_analytic(self.handle, ctypes.byref(desc), obstacles, int(count), out, stream or None))
 
     def build_cellflags(self, grid, accessible, active, mask_batch, flags, stream=0):
         self.lib.check(self.lib.dll.phihip_build_cellflags(self.handle, ctypes.byref(grid), accessible or None, active or None,

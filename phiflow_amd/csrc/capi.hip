@@ -594,10 +594,25 @@ int phihip_centered_vector_to_staggered(phihip_ctx* ctx, const phihip_grid* grid
 static_assert(sizeof(phihip_obstacle) == 4 * 4 + 8 * 21, "phihip_obstacle layout is part of the ABI (phiflow_amd/_capi.py mirrors it)");
 static_assert(sizeof(phihip_solve) == 32 && sizeof(phihip_solve_info) == 32, "ABI structs");
 
-static int check_obstacles(const GridView& v, const phihip_obstacle* obstacles, int count) {
+static int check_obstacles(const phihip_ctx* ctx, const GridView& v, const phihip_obstacle* obstacles, int count) {
     PHIHIP_REQUIRE(count >= 0, "obstacle count must be >= 0");
     PHIHIP_REQUIRE(count == 0 || obstacles != nullptr, "obstacles is NULL");
     for (int k = 0; k < count; ++k) {
+        if (obstacles[k].kind == PHIHIP_OBSTACLE_SDF) {      // f13: a bound signed-distance grid; its own kernels (obstacle_sdf.hpp)
+            const phihip_obstacle& o = obstacles[k];
+            PHIHIP_REQUIRE(ctx != nullptr && o.reserved >= 0 && o.reserved < PHIHIP_SDF_SLOTS && ctx->sdf_bound[o.reserved],
+                           "obstacle %d: SDF slot %d is not bound (phihip_sdf_bind)", k, o.reserved);
+            PHIHIP_REQUIRE(ctx->sdf_slots[o.reserved].rank == v.rank, "obstacle %d: SDF grid of rank %d on a grid of rank %d", k,
+                           ctx->sdf_slots[o.reserved].rank, v.rank);
+            bool spins = false;
+            for (int d = 0; d < 3; ++d) spins = spins || o.angular_velocity[d] != 0.0;
+            if (o.group != 0 || o.embed_mask != 0 || spins) {
+                set_error("obstacle %d: an SDF grid %s", k, o.group != 0 ? "cannot be a member of a union (group != 0)"
+                          : (o.embed_mask != 0 ? "cannot be embedded (embed_mask != 0)" : "cannot have an angular velocity (the geometry does not rotate)"));
+                return PHIHIP_ERR_UNSUPPORTED;
+            }
+            continue;
+        }
         PHIHIP_REQUIRE(obstacles[k].kind == PHIHIP_OBSTACLE_BOX || obstacles[k].kind == PHIHIP_OBSTACLE_SPHERE, "obstacle %d: unknown kind %d", k,
                        obstacles[k].kind);
         const int nh = obstacles[k].kind == PHIHIP_OBSTACLE_SPHERE ? 1 : v.rank;
@@ -629,7 +644,7 @@ int phihip_obstacle_accessible(phihip_ctx* ctx, const phihip_grid* grid, const p
                                void* stream) {
     PHIHIP_ENTER(ctx, grid);
     PHIHIP_REQUIRE(accessible != nullptr, "accessible is NULL");
-    PHIHIP_TRY(check_obstacles(v, obstacles, count));
+    PHIHIP_TRY(check_obstacles(ctx, v, obstacles, count));
     return run_obstacle_accessible(ctx, v, obstacles, count, accessible, s);
 }
 
@@ -637,11 +652,64 @@ int phihip_apply_obstacles(phihip_ctx* ctx, const phihip_grid* grid, const phihi
                            void* stream) {
     PHIHIP_ENTER(ctx, grid);
     PHIHIP_TRY(check_ptrs(v, (const void* const*)velocity, "velocity"));
-    PHIHIP_TRY(check_obstacles(v, obstacles, count));
+    PHIHIP_TRY(check_obstacles(ctx, v, obstacles, count));
     if (count == 0) return PHIHIP_OK;
     void* u[3];
     remap3w(v, velocity, u);
     return run_apply_obstacles(ctx, v, obstacles, count, u, s);
+}
+
+static int check_sdf_desc(const phihip_sdf_grid* d, bool need_values) {
+    PHIHIP_REQUIRE(d != nullptr, "sdf: desc is NULL");
+    PHIHIP_REQUIRE(!need_values || d->sdf != nullptr, "sdf: desc.sdf is NULL");
+    PHIHIP_REQUIRE(d->dtype == PHIHIP_F32 || d->dtype == PHIHIP_F64, "sdf: desc.dtype must be PHIHIP_F32 or PHIHIP_F64");
+    PHIHIP_REQUIRE(d->rank == 2 || d->rank == 3, "sdf: desc.rank must be 2 or 3 (got %d)", d->rank);
+    long long cells = 1;
+    for (int k = 0; k < d->rank; ++k) {
+        PHIHIP_REQUIRE(d->res[k] >= 1, "sdf: desc.res[%d] must be >= 1", k);
+        PHIHIP_REQUIRE(d->upper[k] > d->lower[k], "sdf: bounds must have positive size along axis %d", k);
+        cells *= d->res[k];
+        PHIHIP_REQUIRE(cells < (1LL << 31), "sdf: more than 2^31 values");
+    }
+    return PHIHIP_OK;
+}
+
+int phihip_sdf_bind(phihip_ctx* ctx, const phihip_sdf_grid* desc, int32_t* slot) {
+    PHIHIP_REQUIRE(ctx != nullptr && slot != nullptr, "sdf_bind: ctx / slot is NULL");
+    PHIHIP_TRY(check_sdf_desc(desc, true));
+    for (int k = 0; k < PHIHIP_SDF_SLOTS; ++k)
+        if (!ctx->sdf_bound[k]) {
+            ctx->sdf_slots[k] = *desc;
+            ctx->sdf_bound[k] = true;
+            *slot = k;
+            return PHIHIP_OK;
+        }
+    set_error("sdf_bind: all %d SDF slots of this context are bound (phihip_sdf_release)", PHIHIP_SDF_SLOTS);
+    return PHIHIP_ERR_UNSUPPORTED;
+}
+
+int phihip_sdf_release(phihip_ctx* ctx, int32_t slot) {
+    PHIHIP_REQUIRE(ctx != nullptr, "sdf_release: ctx is NULL");
+    PHIHIP_REQUIRE(slot >= 0 && slot < PHIHIP_SDF_SLOTS && ctx->sdf_bound[slot], "sdf_release: slot %d is not bound", slot);
+    ctx->sdf_bound[slot] = false;
+    return PHIHIP_OK;
+}
+
+int phihip_sdf_from_analytic(phihip_ctx* ctx, const phihip_sdf_grid* desc, const phihip_obstacle* obstacles, int count, void* out, void* stream) {
+    PHIHIP_REQUIRE(ctx != nullptr, "ctx is NULL");
+    PHIHIP_TRY(check_sdf_desc(desc, false));
+    PHIHIP_REQUIRE(out != nullptr, "sdf_from_analytic: out is NULL");
+    PHIHIP_REQUIRE(count >= 1 && obstacles != nullptr, "sdf_from_analytic: at least one obstacle is required");
+    GridView v;
+    memset(&v, 0, sizeof(v));
+    v.rank = desc->rank;
+    v.ax0 = 3 - desc->rank;
+    for (int k = 0; k < count; ++k)
+        PHIHIP_REQUIRE(obstacles[k].kind == PHIHIP_OBSTACLE_BOX || obstacles[k].kind == PHIHIP_OBSTACLE_SPHERE,
+                       "sdf_from_analytic: obstacle %d: kind %d is not analytic (Box / Sphere)", k, obstacles[k].kind);
+    PHIHIP_TRY(check_obstacles(ctx, v, obstacles, count));
+    (void)hipSetDevice(ctx->device);
+    return run_sdf_from_analytic(ctx, v, *desc, obstacles, count, out, (hipStream_t)stream);
 }
 
 int phihip_build_cellflags(phihip_ctx* ctx, const phihip_grid* grid, const uint8_t* accessible, const uint8_t* active, int mask_batch,

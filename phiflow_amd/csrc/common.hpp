@@ -165,6 +165,9 @@ struct phihip_ctx {
     int mg_coarsest = 4;          // coarsen until the smallest axis has at most this many cells
     double mg_omega = 0.8;
     int mg_last_levels = 0, mg_last_launches = 0;   // of the most recent V-cycle (phihip_query_multigrid)
+    // f13: signed-distance grids bound by phihip_sdf_bind (the arrays belong to the caller); an obstacle of kind PHIHIP_OBSTACLE_SDF names a slot
+    phihip_sdf_grid sdf_slots[PHIHIP_SDF_SLOTS] = {};
+    bool sdf_bound[PHIHIP_SDF_SLOTS] = {};
     int adv_last_nblk = 0;        // (tile, plane) units of the most recent LDS-staged advection launch (capacity of its fix-up work list)
     bool adv_ctl_clear = false;   // the work list's control block in ws_adv_flags has been zeroed
     // Adaptive reach (r4). Each LDS-staged pass publishes how many (tile, plane) units fell back to the gather path (the fix-up launch writes
@@ -354,6 +357,8 @@ int run_centered_to_staggered(phihip_ctx*, const GridView&, const void* s, const
                               const double vector[3], int accumulate, void* const out[3], hipStream_t);
 int run_obstacle_accessible(phihip_ctx*, const GridView&, const phihip_obstacle* obs, int count, uint8_t* accessible, hipStream_t);
 int run_apply_obstacles(phihip_ctx*, const GridView&, const phihip_obstacle* obs, int count, void* const v[3], hipStream_t);
+// f13 (obstacle_sdf.hpp): `v` supplies rank / ax0 only
+int run_sdf_from_analytic(phihip_ctx*, const GridView& v, const phihip_sdf_grid& desc, const phihip_obstacle* obs, int count, void* out, hipStream_t);
 int run_balance(phihip_ctx*, const GridView&, const uint8_t* flags, int mask_batch, void* x, hipStream_t);
 int run_advect_staggered_bwd(phihip_ctx*, const GridView&, const void* const f[3], const void* const v[3], const void* const gout[3],
                              void* const gf[3], void* const gv[3], double dt, hipStream_t);

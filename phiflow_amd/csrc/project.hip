@@ -1084,6 +1084,10 @@ __device__ __forceinline__ void decode_box_patch(const PatchBox& pb, int patch, 
     i0 = pb.i0[l] + i;
 }
 
+// f13: obstacles from a signed-distance grid (kind PHIHIP_OBSTACLE_SDF): kernels of their own on the same patches; the two dispatchers below cut
+// the obstacle list into runs of analytic entries -- launched exactly as before -- and single SDF entries
+#include "obstacle_sdf.hpp"
+
 // r3: (4 x 64)-cell patches decoded without integer division (the 64-bit div / mod per cell and the fp64 geometry of EVERY obstacle for
 // EVERY cell made the obstacle kernels run at 1-8 % of the HBM rate); a patch evaluates only the obstacles whose bounding box it touches.
 __global__ __launch_bounds__(kBlock) void obstacle_accessible_kernel(VelGrid g, double lower0, double lower1, double lower2, ObstacleSet s,
@@ -1121,7 +1125,13 @@ int run_obstacle_accessible(phihip_ctx* ctx, const GridView& v, const phihip_obs
     // and visits the patches of their bounding box only (r5)
     PHIHIP_CHECK_HIP(hipMemsetAsync(accessible, 1, (size_t)v.cells, s));
     for (int first = 0; first < count;) {
-        const int n = count - first < kObstaclesPerLaunch ? count - first : kObstaclesPerLaunch;
+        if (obs[first].kind == PHIHIP_OBSTACLE_SDF) {      // f13: one launch of its own, in list order
+            PHIHIP_TRY(run_sdf_accessible(ctx, v, obs[first], accessible, s));
+            ++first;
+            continue;
+        }
+        const int end = analytic_run_end(obs, first, count);
+        const int n = end - first < kObstaclesPerLaunch ? end - first : kObstaclesPerLaunch;
         const ObstacleSet set = make_obstacle_set(v, obs, first, n);
         PatchBox pb;
         memset(&pb, 0, sizeof(pb));
@@ -1210,9 +1220,15 @@ int run_apply_obstacles(phihip_ctx* ctx, const GridView& v, const phihip_obstacl
     for (int a = v.ax0; a < 3; ++a) r2 += 0.25 * v.dx[a] * v.dx[a];
     const double radius = sqrt(r2);
     for (int first = 0, n = 0; first < count; first += n) {
-        n = count - first < kObstaclesPerLaunch ? count - first : kObstaclesPerLaunch;
+        if (obs[first].kind == PHIHIP_OBSTACLE_SDF) {      // f13: the obstacles apply one after the other (fluid.py:226-240): an SDF entry ends a run
+            PHIHIP_TRY(run_sdf_apply(ctx, v, obs[first], vel, s));
+            n = 1;
+            continue;
+        }
+        const int end = analytic_run_end(obs, first, count);
+        n = end - first < kObstaclesPerLaunch ? end - first : kObstaclesPerLaunch;
         // a union is applied by ONE launch: do not cut inside a group
-        while (n > 0 && first + n < count && obs[first + n].group != 0 && obs[first + n].group == obs[first + n - 1].group) --n;
+        while (n > 0 && first + n < end && obs[first + n].group != 0 && obs[first + n].group == obs[first + n - 1].group) --n;
         if (n == 0) {
             set_error("apply_obstacles: a union (group %d) has more than %d members", obs[first].group, kObstaclesPerLaunch);
             return PHIHIP_ERR_UNSUPPORTED;

@@ -14,14 +14,14 @@ import torch
 from . import _capi, autodiff
 from .extrapolation import pressure_extrapolation
 from .field import Field, _check_pressure_padding, _ptrs, same_grid
-from .geom import Box, Geometry, Sphere
+from .geom import Box, Geometry, SDFGrid, Sphere
 from .geom import Embedded, Union as Union_
 from .solve import Diverged, NotConverged, Solve, SolveInfo
 
 
 class Obstacle:
     """ An obstacle defines boundary conditions inside a geometry; it can have a linear and an angular velocity
-    (phi/physics/fluid.py:21-91). Geometries: `Box` / `Cuboid` and `Sphere`. """
+    (phi/physics/fluid.py:21-91). Geometries: `Box` / `Cuboid`, `Sphere`, unions and embeddings of them, and `SDFGrid` (any shape; linear velocity only). """
 
     def __init__(self, geometry: Geometry, velocity=0, angular_velocity=0):
         self.geometry = geometry
@@ -102,6 +102,18 @@ def _obstacle_array(obstacles: Sequence[Obstacle], velocity: Field, entry: int =
                 raise NotImplementedError("HIP backend: a union obstacle cannot have an angular velocity")
         for geo in members:
             embed_mask = 0
+            inner_sdf = geo.geometry if isinstance(geo, Embedded) else geo
+            if isinstance(inner_sdf, SDFGrid):   # f13: a bound signed-distance grid, kernels of its own (csrc/obstacle_sdf.hpp)
+                if len(members) > 1:
+                    raise NotImplementedError("HIP backend: an SDFGrid inside union(...) is not supported (pass it as an obstacle of its own)")
+                if isinstance(geo, Embedded):
+                    raise NotImplementedError("HIP backend: an SDFGrid inside embed(...) is not supported")
+                if ob.is_rotating:
+                    raise NotImplementedError("HIP backend: an Obstacle on an SDFGrid cannot have an angular velocity (the geometry does not rotate)")
+                order = [geo.dims.index(d) for d in velocity.dims]
+                items.append(dict(kind=_capi.OBSTACLE_SDF, slot=geo.device_slot(velocity.backend, order),
+                                  velocity=[ob.velocity[ob.geometry.dims.index(d)] for d in velocity.dims]))
+                continue
             if isinstance(geo, Embedded):   # infinitely long along the dims the inner geometry lacks
                 if ob.is_rotating:
                     raise NotImplementedError("HIP backend: an embedded geometry (embed / infinite_cylinder) cannot have an angular velocity")
@@ -120,7 +132,7 @@ def _obstacle_array(obstacles: Sequence[Obstacle], velocity: Field, entry: int =
             elif isinstance(geo, Box):
                 kind, half = _capi.OBSTACLE_BOX, [geo.half_size[i] for i in order]
             else:
-                raise NotImplementedError(f"HIP backend: obstacle geometry {type(geo).__name__} is not supported (Box / Cuboid / Sphere / union)")
+                raise NotImplementedError(f"HIP backend: obstacle geometry {type(geo).__name__} is not supported (Box / Cuboid / Sphere / union / SDFGrid)")
             vel_order = [ob.geometry.dims.index(d) for d in velocity.dims]
             ang = ob.angular_velocity if len(order) == 2 else [ob.angular_velocity[i] for i in vel_order]
             rot = None
@@ -198,7 +210,7 @@ def make_incompressible(velocity: Field,
 
     Args:
         velocity: `StaggeredGrid`.
-        obstacles: `Obstacle` or `Geometry` or tuple/list thereof (Box / Cuboid / Sphere; stationary, moving or rotating).
+        obstacles: `Obstacle` or `Geometry` or tuple/list thereof (Box / Cuboid / Sphere; stationary, moving or rotating; `SDFGrid` for any other shape: stationary or moving).
         solve: `Solve` object specifying tolerances, `x0` (pressure guess) and `max_iterations`.
         active: (Optional) `CenteredGrid` mask for which cells the pressure should be solved. If given, the total
             divergence is never subtracted, even if all values are 1.
@@ -313,7 +325,7 @@ def _apply_obstacles_autograd(velocity: Field, obstacles, vin):
     _require_staggered_velocity(velocity, 'apply_boundary_conditions')
     still = [Obstacle(ob.geometry) for ob in obstacles]
     arr, count = _obstacle_array(obstacles, velocity)
-    meta = dict(be=velocity.backend, grid=velocity.grid_struct(), obstacles=arr, obstacles_still=_obstacle_array(still, velocity)[0], count=count,
+    meta = dict(be=velocity.backend, grid=velocity.grid_struct(), obstacles=arr, obstacles_still=_obstacle_array(still, velocity)[0], count=count, keep_alive=obstacles,      # (an SDFGrid's slot lives as long as the geometry)
                 shapes=[tuple(t.shape) for t in vin], dtype=velocity.dtype)
     return autodiff.ApplyObstacles.apply(meta, *vin)
 

@@ -1,6 +1,7 @@
 """
 Geometry subset needed by the grid fluid step: `Box` / `Cuboid` (domain bounds and box obstacles, optionally rotated) and
-`Sphere` (reference: phi/geom/_box.py:46-236, phi/geom/_sphere.py). Obstacles are rasterised by device kernels
+`Sphere` (reference: phi/geom/_box.py:46-236, phi/geom/_sphere.py), and `SDFGrid` / `sample_sdf` for every other shape (a grid of signed distances,
+phi/geom/_sdf_grid.py:13-298; at the end of this file). Obstacles are rasterised by device kernels
 (`phihip_obstacle_accessible`, `phihip_apply_obstacles`); the host-side `lies_inside` / `approximate_signed_distance` below only
 serve field initialisers such as `CenteredGrid(Sphere(...))`.
 """
@@ -336,3 +337,274 @@ class Sphere(Geometry):
 
     def __repr__(self):
         return f"Sphere({dict(zip(self.dims, self.center))}, radius={self.radius})"
+
+
+# ---- f13: arbitrary shapes from a signed-distance grid (phi/geom/_sdf_grid.py) ------------------------------------------------------
+def _multilinear_clamped(values: np.ndarray, idx: Sequence[np.ndarray]) -> np.ndarray:
+    """ math.grid_sample(values, idx, ZERO_GRADIENT): multilinear interpolation, every tap index clamped to [0, n - 1] [PHIML-RECALL]
+    (phiflow_amd/csrc/obstacle_sdf.hpp sdf_sample takes the same steps in the same order: last axis first) """
+    D = values.ndim
+    shape = np.broadcast(*idx).shape
+    lo, hi, f = [], [], []
+    for a in range(D):
+        n = values.shape[a]
+        c = np.clip(np.broadcast_to(np.asarray(idx[a], np.float64), shape), -1.0, float(n))
+        fl = np.floor(c)
+        f.append(c - fl)
+        lo.append(np.clip(fl.astype(np.int64), 0, n - 1))
+        hi.append(np.clip(fl.astype(np.int64) + 1, 0, n - 1))
+    v = values.astype(np.float64)
+
+    def level(a, index):
+        if a == D:
+            return v[tuple(index)]
+        return level(a + 1, index + [lo[a]]) * (1.0 - f[a]) + level(a + 1, index + [hi[a]]) * f[a]
+    return level(0, [])
+
+
+class SDFGrid(Geometry):
+    """ `SDFGrid(sdf, bounds)`: a geometry given by signed-distance values at the centres of the virtual cells of `bounds`
+    (phi/geom/_sdf_grid.py:13-243). With res the array's resolution and size that of the bounds:
+        sdf_val(x)                     = multilinear(sdf, (x - lower) / size * res - 0.5), taps clamped           (:150-151, :184-185)
+        lies_inside(x)                 = [bounds.lies_inside(x) &] sdf_val <= 0, both inclusive                    (:149-156)
+        approximate_signed_distance(x) = sdf_val [inside the bounds, |x - center| - bounding_radius outside]       (:183-191)
+    the bracketed parts with `approximate_outside` (the constructor's default; `sample_sdf`'s default is False). Without it an edge
+    value <= 0 extends to infinity.
+
+    sdf: NumPy array or torch tensor with the spatial shape in the order of `bounds.dims`; a leading batch axis gives one geometry per batch
+    entry (`Batched`). fp32 and fp64 values are kept as they are, anything else becomes fp64. As an obstacle the values live on the device
+    (a torch tensor that already does is used in place and kept alive by this object); the kernels of csrc/obstacle_sdf.hpp sample them.
+    The host queries below serve `resample(geometry, ...)`, `field.where(geometry, ...)` and field initialisers. """
+
+    def __new__(cls, sdf=None, bounds=None, *args, **kwargs):
+        if sdf is not None and bounds is not None and np.ndim(sdf) == len(bounds.dims) + 1 and kwargs.get('_shared') is None:
+            return Batched([SDFGrid(sdf[b], bounds, *args, **kwargs) for b in range(len(sdf))])
+        return super().__new__(cls)
+
+    def __init__(self, sdf, bounds: Box, approximate_outside=True, gradient=None, to_surface=None, surf_normal=None, surf_index=None,
+                 center=None, volume=None, bounding_radius=None, _shared=None):
+        for name, arg in (("gradient", gradient), ("to_surface", to_surface), ("surf_normal", surf_normal), ("surf_index", surf_index)):
+            if arg is not None:
+                raise NotImplementedError(f"HIP backend: SDFGrid({name}=...) is not implemented (surface look-ups are not part of the fluid step)")
+        assert isinstance(bounds, Box) and bounds.rot is None, "SDFGrid bounds must be an axis-aligned Box"
+        self.dims = bounds.dims
+        self.bounds = bounds
+        self.approximate_outside = bool(approximate_outside)
+        D = len(self.dims)
+        if _shared is not None:      # shifted / scaled: the same array, host and device
+            self._host, self._digest, self._device = _shared
+        else:
+            self._device = {}        # str(torch device) -> tensor (kept alive here)
+            try:
+                import torch
+            except ImportError:
+                torch = None
+            if torch is not None and isinstance(sdf, torch.Tensor):
+                if sdf.requires_grad:
+                    raise NotImplementedError("HIP backend: an SDFGrid whose `sdf` tensor requires grad is not supported (no gradients with respect to the SDF values)")
+                if sdf.dtype not in (torch.float32, torch.float64):
+                    sdf = sdf.to(torch.float64)
+                sdf = sdf.detach().contiguous()
+                self._device[str(sdf.device)] = sdf
+                host = sdf.cpu().numpy()
+            else:
+                host = np.asarray(sdf)
+            if host.dtype not in (np.float32, np.float64):
+                host = host.astype(np.float64)
+            self._host = np.ascontiguousarray(host)
+            import hashlib
+            self._digest = hashlib.sha1(self._host.tobytes()).hexdigest()[:16]
+        assert self._host.ndim == D and self._host.size > 0, f"sdf must have one axis per dimension of the bounds {self.dims}, got shape {self._host.shape}"
+        self._slots = {}             # id(backend) -> (context, slot)
+        res = self._host.shape
+        lower, size = np.asarray(bounds.lower), np.asarray(bounds.size)
+        if center is not None:
+            c = [center[d] for d in self.dims] if isinstance(center, dict) else list(center)
+            self.center = tuple(float(x) for x in c)
+        else:       # bounds.local_to_global(argmin_index / res): the LOWER CORNER of the minimum cell, not its centre (:51-52, restated as written)
+            arg = np.unravel_index(int(np.argmin(self._host)), res)
+            self.center = tuple(float(lower[a] + (arg[a] / res[a]) * size[a]) for a in range(D))
+        dx = size / np.asarray(res)
+        self.volume = float(volume) if volume is not None else float((self._host < 0).sum() * np.prod(dx))      # :56-57
+        if bounding_radius is not None:
+            self._bounding_radius = float(bounding_radius)
+        else:       # the farthest cell centre with sdf <= 0 from `center` (:61-64)
+            pts = [(lower[a] + (np.arange(res[a]) + 0.5) * dx[a]).reshape([-1 if k == a else 1 for k in range(D)]) for a in range(D)]
+            dist = np.sqrt(sum((p - c) ** 2 for p, c in zip(pts, self.center)))
+            self._bounding_radius = float(np.where(self._host <= 0, dist, 0.0).max())
+
+    # ---- properties of the reference class ----
+    @property
+    def values(self) -> np.ndarray:
+        return self._host
+
+    @property
+    def resolution(self) -> Dict[str, int]:
+        return dict(zip(self.dims, self._host.shape))
+
+    @property
+    def size(self):
+        return self.bounds.size
+
+    @property
+    def dx(self):
+        return tuple(s / n for s, n in zip(self.bounds.size, self._host.shape))
+
+    def bounding_radius(self) -> float:
+        return self._bounding_radius
+
+    def bounding_half_extent(self):
+        """ bounds.half_size -- "this could be too small if the center is not in the middle of the bounds" (:199-200) """
+        return self.bounds.half_size
+
+    # ---- host queries ----
+    def _sample(self, points):
+        res = self._host.shape
+        idx = [(np.asarray(points[a], np.float64) - self.bounds.lower[a]) / self.bounds.size[a] * float(res[a]) - 0.5 for a in range(len(self.dims))]
+        return _multilinear_clamped(self._host, idx)
+
+    def lies_inside(self, points):
+        inside = self._sample(points) <= 0
+        return (self.bounds.lies_inside(points) & inside) if self.approximate_outside else inside
+
+    def approximate_signed_distance(self, points):
+        val = self._sample(points)
+        if not self.approximate_outside:
+            return val
+        d2 = sum((np.asarray(p, np.float64) - c) ** 2 for p, c in zip(points, self.center))
+        return np.where(self.bounds.lies_inside(points), val, np.sqrt(d2) - self._bounding_radius)
+
+    # ---- transforms ----
+    def _with(self, bounds, center, volume, radius):
+        return SDFGrid(None, bounds, self.approximate_outside, center=center, volume=volume, bounding_radius=radius,
+                       _shared=(self._host, self._digest, self._device))
+
+    def shifted(self, delta):
+        """ moves bounds and center, shares the array (:202-203) """
+        delta = [delta.get(d, 0.0) for d in self.dims] if isinstance(delta, dict) else list(delta)
+        return self._with(self.bounds.shifted(delta), tuple(c + dd for c, dd in zip(self.center, delta)), self.volume, self._bounding_radius)
+
+    def at(self, center):
+        """ shifted(center - self.center) (:205-206) """
+        center = [center.get(d, c) for d, c in zip(self.dims, self.center)] if isinstance(center, dict) else list(center)
+        return self.shifted([c - s for c, s in zip(center, self.center)])
+
+    def rotated(self, angle):
+        raise NotImplementedError("SDF does not yet support rotation")      # (:208-209)
+
+    def scaled(self, factor):
+        """ :211-215: the bounds grow by `factor` about their own centre and move by off_center * (factor - 1); center stays """
+        factor = float(factor)
+        off = [c - b for c, b in zip(self.center, self.bounds.center)]
+        b = self.bounds
+        grown = Box(**{d: (c - h * factor, c + h * factor) for d, c, h in zip(b.dims, b.center, b.half_size)}).shifted([o * (factor - 1) for o in off])
+        return self._with(grown, self.center, self.volume * factor ** len(self.dims), self._bounding_radius * factor)
+
+    def __repr__(self):
+        # (fluid._MaskCache keys on this: it changes with the bounds, the flag, center / radius and the values)
+        return (f"SDFGrid({'x'.join(map(str, self._host.shape))} {self._host.dtype.name} #{self._digest}, {self.bounds!r}, approximate_outside={self.approximate_outside}, "
+                f"center={self.center}, bounding_radius={self._bounding_radius})")
+
+    # ---- device side ----
+    def device_values(self, backend):
+        """ the values on the backend's device: the tensor this object was built from if it lives there, else one upload (shared with shifted copies) """
+        import torch
+        key = str(backend.device)
+        if key not in self._device:
+            self._device[key] = torch.from_numpy(self._host).to(backend.device).contiguous()
+        return self._device[key]
+
+    def device_slot(self, backend, order) -> int:
+        """ slot of this grid in the backend's context (bound on first use, released with this object); `order`: the positions of the velocity's
+        dimensions among self.dims -- the array itself must already be in that order """
+        key = id(backend.ctx)
+        if key not in self._slots:
+            if list(order) != sorted(order):
+                raise NotImplementedError(f"HIP backend: an SDFGrid with dimensions {self.dims} meets a velocity whose dimensions are in another order")
+            t = self.device_values(backend)
+            from . import _capi
+            import torch
+            import weakref
+            desc = _capi.make_sdf_grid(t.data_ptr(), _capi.PHIHIP_F64 if t.dtype == torch.float64 else _capi.PHIHIP_F32, self._host.shape, self.bounds.lower,
+                                       self.bounds.upper, self.center, self._bounding_radius, self.approximate_outside)
+            slot = backend.ctx.sdf_bind(desc)
+            self._slots[key] = slot
+            weakref.finalize(self, _release_sdf_slot, weakref.ref(backend.ctx), slot)
+        return self._slots[key]
+
+
+def _release_sdf_slot(ctx_ref, slot):
+    ctx = ctx_ref()
+    if ctx is not None and ctx.handle:
+        try:
+            ctx.sdf_release(slot)
+        except Exception:      # (interpreter shutdown: the library may be gone)
+            pass
+
+
+def _bounding_box(geometry: Geometry) -> Box:
+    """ Geometry.bounding_box (phi/geom/_geom.py:360-373): center -+ bounding_half_extent; a union: the box around its members' boxes
+    (phi/geom/_geom_ops.py:68-70) """
+    if isinstance(geometry, Union):
+        boxes = [_bounding_box(g) for g in geometry.geometries]
+        return Box(**{d: (min(b.lower[b.dims.index(d)] for b in boxes), max(b.upper[b.dims.index(d)] for b in boxes)) for d in geometry.dims})
+    if isinstance(geometry, Sphere):
+        return Box(**{d: (c - geometry.radius, c + geometry.radius) for d, c in zip(geometry.dims, geometry.center)})
+    if isinstance(geometry, Box):
+        half = geometry.half_size if geometry.rot is None else tuple(np.abs(geometry.rot) @ np.asarray(geometry.half_size))      # _box.py:168-172
+        return Box(**{d: (c - h, c + h) for d, c, h in zip(geometry.dims, geometry.center, half)})
+    if isinstance(geometry, SDFGrid):
+        return Box(**{d: (c - h, c + h) for d, c, h in zip(geometry.dims, geometry.center, geometry.bounding_half_extent())})
+    raise NotImplementedError(f"HIP backend: sample_sdf of {type(geometry).__name__} is not supported (Box / Cuboid / Sphere / union)")
+
+
+def sample_sdf(geometry: Geometry, bounds: Box = None, resolution: Dict[str, int] = None, approximate_outside=False, rebuild=None, valid_dist=None,
+               rel_margin=.1, abs_margin=0., cache_surface=False, dtype=np.float32, backend=None, **resolution_) -> SDFGrid:
+    """ `sample_sdf(geometry, bounds, x=64, y=32)` (phi/geom/_sdf_grid.py:245-298): an SDFGrid of `geometry.approximate_signed_distance` at the
+    centres of the cells of `bounds`; center, volume and bounding_radius come from the geometry (a union: the centre of its bounding box, the
+    other two from the grid). Default bounds: the geometry's bounding box with half_size * (1 + 2 rel_margin) + 2 abs_margin (:273-274).
+    `approximate_outside` defaults to False here and to True in `SDFGrid(...)`, as in the reference. Box / Cuboid (rotated too), Sphere and
+    unions of them are evaluated on the device (`phihip_sdf_from_analytic`); `dtype`: element type of the array. """
+    if rebuild is not None or cache_surface or valid_dist is not None:
+        what = "rebuild" if rebuild is not None else ("cache_surface" if cache_surface else "valid_dist")
+        raise NotImplementedError(f"HIP backend: sample_sdf({what}=...) is not implemented (SDF values are queried from the geometry)")
+    if geometry.batch_size > 1:
+        return Batched([sample_sdf(geometry.entry(b), bounds, resolution, approximate_outside, None, None, rel_margin, abs_margin, False, dtype, backend,
+                                   **resolution_) for b in range(geometry.batch_size)])
+    res = dict(resolution or {}, **resolution_)
+    if bounds is None:
+        bb = _bounding_box(geometry)
+        bounds = Box(**{d: (c - (h * (1 + 2 * rel_margin) + 2 * abs_margin), c + (h * (1 + 2 * rel_margin) + 2 * abs_margin))
+                        for d, c, h in zip(bb.dims, bb.center, bb.half_size)})
+    assert set(res) == set(bounds.dims) == set(geometry.dims), f"sample_sdf needs a resolution for every dimension of {bounds.dims}, got {tuple(res)}"
+    members = geometry.geometries if isinstance(geometry, Union) else (geometry,)
+    dims = bounds.dims
+    items = []
+    for g in members:
+        order = [g.dims.index(d) for d in dims]
+        if isinstance(g, Sphere):
+            items.append(dict(kind=1, center=[g.center[i] for i in order], half_size=[g.radius] * len(order)))
+        elif isinstance(g, Box):
+            rot = None if g.rot is None else [[g.rot[i][j] for j in order] for i in order]
+            items.append(dict(kind=0, center=[g.center[i] for i in order], half_size=[g.half_size[i] for i in order], rotation=rot))
+        else:
+            raise NotImplementedError(f"HIP backend: sample_sdf of {type(g).__name__} is not supported (Box / Cuboid / Sphere / union)")
+    import torch
+    from . import _capi
+    from .backend import default_backend
+    be = backend if backend is not None else default_backend()
+    tdtype = torch.float64 if np.dtype(dtype) == np.float64 else torch.float32
+    shape = tuple(int(res[d]) for d in dims)
+    out = be.empty(shape, tdtype)
+    desc = _capi.make_sdf_grid(0, _capi.PHIHIP_F64 if tdtype == torch.float64 else _capi.PHIHIP_F32, shape, bounds.lower, bounds.upper, bounds.center, 0.0, approximate_outside)
+    be.ctx.sdf_from_analytic(desc, _capi.make_obstacles(items), len(items), out.data_ptr(), be.stream())
+    if isinstance(geometry, Union):
+        return SDFGrid(out, bounds, approximate_outside, center=_bounding_box(geometry).center)
+    if isinstance(geometry, Sphere):
+        D = len(dims)
+        volume = {2: np.pi * geometry.radius ** 2, 3: 4 / 3 * np.pi * geometry.radius ** 3}.get(D, 2 * geometry.radius)
+        center, radius = [geometry.center[geometry.dims.index(d)] for d in dims], geometry.radius
+    else:
+        volume = float(np.prod(geometry.size))
+        center, radius = [geometry.center[geometry.dims.index(d)] for d in dims], float(np.sqrt(sum(h * h for h in geometry.half_size)))      # _box.py:209-210
+    return SDFGrid(out, bounds, approximate_outside, center=center, volume=volume, bounding_radius=radius)
