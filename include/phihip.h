@@ -542,6 +542,26 @@ int phihip_curl_2d(phihip_ctx* ctx, const phihip_grid* grid, int staggered, cons
 int phihip_curl_2d_backward(phihip_ctx* ctx, const phihip_grid* grid, int staggered, const int32_t s_bc[3][2], const void* grad_out, void* grad_vx,
                             void* grad_vy, void* stream);
 
+/* The finite-difference advection term -(velocity . grad) u, order 2 (phi/physics/advect.py:78-133 `differential`). One launch for all
+ * components and batch entries; u_batch / velocity_batch are 1 (shared by every entry) or grid.batch. Component c of u is padded by one sample with
+ * its own extrapolation (PERIODIC wraps, OPEN copies the edge sample, CLOSED is the component's constant).
+ * Staggered (advect.py:108-116), u and velocity on the grid's stored faces with the grid's boundary:
+ *   out_c[f] = -sum_d W_d(f) (U_c[f + e_d] - U_c[f - e_d]) / (2 dx_d),  W_c(f) = velocity_c[f],  W_d(f) = the mean of the four d-faces around f (d != c;
+ *   a face that is not stored comes from the velocity's padding: `vel.at(grad)`, phi/field/_resample.py:279-287).
+ * The *_backward entries ACCUMULATE the gradients w.r.t. u and w.r.t. the velocity (gathers, no atomics; every array has grid.batch entries); either
+ * gradient may be NULL. When u is the velocity the caller adds the two. */
+int phihip_advect_differential(phihip_ctx* ctx, const phihip_grid* grid, const void* const u[3], int u_batch, const void* const velocity[3],
+                               int velocity_batch, void* const out[3], void* stream);
+int phihip_advect_differential_backward(phihip_ctx* ctx, const phihip_grid* grid, const void* const u[3], const void* const velocity[3],
+                                        const void* const grad_out[3], void* const grad_u[3], void* const grad_velocity[3], void* stream);
+/* Centred vector fields [batch][rank][cells] on one grid (advect.py:117-124): out_c[i] = -sum_d velocity_d[i] (U_c[i + e_d] - U_c[i - e_d]) / (2 dx_d);
+ * s_bc / s_val: the extrapolation of u (shared by its components). */
+int phihip_advect_differential_centered(phihip_ctx* ctx, const phihip_grid* grid, const void* u, int u_batch, const int32_t s_bc[3][2],
+                                        const double s_val[3][2], const void* velocity, int velocity_batch, void* out, void* stream);
+int phihip_advect_differential_centered_backward(phihip_ctx* ctx, const phihip_grid* grid, const void* u, const int32_t s_bc[3][2],
+                                                 const double s_val[3][2], const void* velocity, const void* grad_out, void* grad_u,
+                                                 void* grad_velocity, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

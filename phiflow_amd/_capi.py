@@ -37,6 +37,8 @@ EXPORTED_SYMBOLS = (
     "phihip_field_laplace", "phihip_field_laplace_centered", "phihip_gradient_centered", "phihip_gradient_centered_backward",
     "phihip_divergence_centered", "phihip_divergence_centered_backward", "phihip_curl_2d", "phihip_curl_2d_backward",
     "phihip_sdf_bind", "phihip_sdf_release", "phihip_sdf_from_analytic",
+    "phihip_advect_differential", "phihip_advect_differential_backward", "phihip_advect_differential_centered",
+    "phihip_advect_differential_centered_backward",
 )
 
 
@@ -277,6 +279,11 @@ class Library:
         d.phihip_divergence_centered_backward.argtypes = [c_void_p, POINTER(Grid), _bc, c_void_p, c_void_p, c_void_p]
         d.phihip_curl_2d.argtypes = [c_void_p, POINTER(Grid), c_int, c_void_p, c_void_p, _bc, _val, c_void_p, c_void_p]
         d.phihip_curl_2d_backward.argtypes = [c_void_p, POINTER(Grid), c_int, _bc, c_void_p, c_void_p, c_void_p, c_void_p]
+        d.phihip_advect_differential.argtypes = [c_void_p, POINTER(Grid), POINTER(_Ptr3), c_int, POINTER(_Ptr3), c_int, POINTER(_Ptr3), c_void_p]
+        d.phihip_advect_differential_backward.argtypes = [c_void_p, POINTER(Grid), POINTER(_Ptr3), POINTER(_Ptr3), POINTER(_Ptr3), POINTER(_Ptr3), POINTER(_Ptr3),
+                                                          c_void_p]
+        d.phihip_advect_differential_centered.argtypes = [c_void_p, POINTER(Grid), c_void_p, c_int, _bc, _val, c_void_p, c_int, c_void_p, c_void_p]
+        d.phihip_advect_differential_centered_backward.argtypes = [c_void_p, POINTER(Grid), c_void_p, _bc, _val, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
         d.phihip_sdf_bind.argtypes = [c_void_p, POINTER(SdfGridStruct), POINTER(c_int32)]
         d.phihip_sdf_release.argtypes = [c_void_p, c_int32]
         d.phihip_sdf_from_analytic.argtypes = [c_void_p, POINTER(SdfGridStruct), POINTER(ObstacleStruct), c_int, c_void_p, c_void_p]
@@ -621,6 +628,27 @@ class Context:
         bc, _ = self._scalar_bc(grid, s_bc, None)
         self.lib.check(self.lib.dll.phihip_curl_2d_backward(self.handle, ctypes.byref(grid), int(bool(staggered)), ctypes.byref(bc), grad_out, grad_vx,
                                                             grad_vy or None, stream or None))
+
+    # --- the finite-difference advection term (csrc/momentum.hpp); the *_backward entries accumulate, a gradient that is None is skipped ---
+    def advect_differential(self, grid, u, u_batch, velocity, velocity_batch, out, stream=0):
+        self.lib.check(self.lib.dll.phihip_advect_differential(self.handle, ctypes.byref(grid), ctypes.byref(ptr3(u)), int(u_batch), ctypes.byref(ptr3(velocity)),
+                                                               int(velocity_batch), ctypes.byref(ptr3(out)), stream or None))
+
+    def advect_differential_backward(self, grid, u, velocity, grad_out, grad_u, grad_velocity, stream=0):
+        gu = ctypes.byref(ptr3(grad_u)) if grad_u is not None else None
+        gv = ctypes.byref(ptr3(grad_velocity)) if grad_velocity is not None else None
+        self.lib.check(self.lib.dll.phihip_advect_differential_backward(self.handle, ctypes.byref(grid), ctypes.byref(ptr3(u)), ctypes.byref(ptr3(velocity)),
+                                                                        ctypes.byref(ptr3(grad_out)), gu, gv, stream or None))
+
+    def advect_differential_centered(self, grid, u, u_batch, s_bc, s_val, velocity, velocity_batch, out, stream=0):
+        bc, val = self._scalar_bc(grid, s_bc, s_val)
+        self.lib.check(self.lib.dll.phihip_advect_differential_centered(self.handle, ctypes.byref(grid), u, int(u_batch), ctypes.byref(bc), ctypes.byref(val), velocity,
+                                                                        int(velocity_batch), out, stream or None))
+
+    def advect_differential_centered_backward(self, grid, u, s_bc, s_val, velocity, grad_out, grad_u, grad_velocity, stream=0):
+        bc, val = self._scalar_bc(grid, s_bc, s_val)
+        self.lib.check(self.lib.dll.phihip_advect_differential_centered_backward(self.handle, ctypes.byref(grid), u, ctypes.byref(bc), ctypes.byref(val), velocity,
+                                                                                 grad_out, grad_u or None, grad_velocity or None, stream or None))
 
     def diffuse_implicit_centered_coef(self, grid, s, s_bc, s_val, coef, c_batch, c_bc, c_val, kdt, out, solve: Solve, stream=0, want_info=True):
         """ diffuse.implicit with a varying / per-axis diffusivity; returns [batch] SolveInfo (None with want_info=False: no host read-back) """

@@ -2,7 +2,8 @@
 Advection schemes backed by libphihip (reference: phi/physics/advect.py).
 Implemented on the HIP backend: `semi_lagrangian` / `advect` / `mac_cormack` with the `euler` (fused kernels) and `rk4` / `finite_rk4` integrators for StaggeredGrid
 and CenteredGrid fields advected by a StaggeredGrid velocity, and for centred scalar / vector fields advected by a centred vector velocity (Burgers'
-equation: `advect.semi_lagrangian(v, v, dt)` of a CenteredGrid). Anything else raises `NotImplementedError`.
+equation: `advect.semi_lagrangian(v, v, dt)` of a CenteredGrid), and `differential` / `finite_difference`, the central-difference term -(v . grad) u
+of a method-of-lines step. Anything else raises `NotImplementedError`.
 """
 from typing import Callable
 
@@ -140,6 +141,69 @@ def _advect_by_centered(field: Field, velocity: Field, dt: float, integrator: Ca
 def advect(field: Field, velocity: Field, dt: float, integrator: Callable = euler) -> Field:
     """ `advect.advect` for grids == `semi_lagrangian` (phi/physics/advect.py:50-75) """
     return semi_lagrangian(field, velocity, dt, integrator=integrator)
+
+
+def differential(u: Field, velocity: Field, density: float = 1., order=2, implicit=None, upwind=True) -> Field:
+    """ The differential advection term -(velocity . grad) u as it stands on the right-hand side of a PDE, with central differences
+    (phi/physics/advect.py:78-133, grid branches :108-124; csrc/momentum.hpp). `density` and `upwind` are accepted and, as in the
+    reference's grid branches, not read.
+
+    StaggeredGrid `u` with a StaggeredGrid `velocity` on the same grid and boundary (`u` may be the velocity itself): for component c at its stored face f
+    `-sum_d W_d(f) (U_c[f + e_d] - U_c[f - e_d]) / (2 dx_d)` with W_c = velocity_c[f] and W_d the mean of the four d-faces around f; the result has u's
+    boundary and face layout. Centred vector `u` with a centred vector `velocity`: `-sum_d velocity_d[i] (U_c[i + e_d] - U_c[i - e_d]) / (2 dx_d)`; the
+    result carries the VELOCITY's boundary (advect.py:124). U_c is component c padded with its own extrapolation. A batch of 1 on either side is shared.
+    Differentiable w.r.t. u and the velocity. """
+    from . import _capi
+    from .field import _cell_grid, _centered_rule, require_plain, same_grid
+    require_plain(u, 'advect.differential'); require_plain(velocity, 'advect.differential (velocity)')
+    if order != 2:
+        raise NotImplementedError(f"HIP backend: advect.differential implements order=2 only (got order={order}); pass order=2")
+    if implicit is not None:
+        raise NotImplementedError("HIP backend: advect.differential computes explicit stencils only; pass implicit=None")
+    if u.spatial_rank not in (2, 3):
+        raise NotImplementedError(f"HIP backend: advect.differential on {u.spatial_rank}-D grids is not implemented (2-D and 3-D only)")
+    if u.is_centered and not u.is_vector:
+        raise NotImplementedError("HIP backend: advect.differential of a centred SCALAR field is not implemented (the reference iterates `u.vector`); advect "
+                                  "scalars with advect.semi_lagrangian / mac_cormack, or pass a vector field")
+    if velocity.is_staggered != u.is_staggered or (velocity.is_centered and not velocity.is_vector) or not same_grid(u, velocity):
+        raise NotImplementedError("HIP backend: advect.differential needs u and velocity of the same kind (both StaggeredGrid or both centred vector fields) "
+                                  "on the same grid; resample one with `@` first")
+    assert u.dtype == velocity.dtype, "u and velocity must have the same precision"
+    be = velocity.backend
+    B = max(u.batch_size, velocity.batch_size)
+    assert u.batch_size in (1, B) and velocity.batch_size in (1, B), f"batch sizes {u.batch_size} and {velocity.batch_size} do not match"
+    batched = u.batched or velocity.batched
+    same = u is velocity
+    if u.is_staggered:
+        if [tuple(a.shape[1:]) for a in u.values] != [tuple(b.shape[1:]) for b in velocity.values] or \
+                resolve(u.boundary, u.dims) != resolve(velocity.boundary, velocity.dims):
+            raise NotImplementedError("HIP backend: advect.differential of a StaggeredGrid needs u to share the velocity's boundary conditions; "
+                                      "`u.with_boundary(velocity.boundary)` re-stores it")
+        grid = velocity.grid_struct(batch=B)
+        uv = [t.contiguous() for t in u.values]
+        vv = uv if same else [t.contiguous() for t in velocity.values]
+        if autodiff.needs_grad(*uv, *vv):
+            meta = dict(be=be, grid=grid, rank=u.spatial_rank, same=same)
+            args = uv if same else [_expand(t, B) for t in uv] + [_expand(t, B) for t in vv]
+            out = list(autodiff.AdvectDifferentialStaggered.apply(meta, *args))
+        else:
+            out = [be.empty((B,) + tuple(t.shape[1:]), u.dtype) for t in uv]
+            be.ctx.advect_differential(grid, _ptrs(uv), u.batch_size, _ptrs(vv), velocity.batch_size, _ptrs(out), be.stream())
+        return Field(u.resolution, u.bounds, u.boundary, out, True, be, batched)
+    s_codes, s_val = _centered_rule(u, 'advect.differential')
+    grid = _cell_grid(u, B)
+    src = u.values.contiguous()
+    vel = src if same else velocity.values.contiguous()
+    if autodiff.needs_grad(src, vel):
+        meta = dict(be=be, grid=grid, s_codes=s_codes, s_val=s_val, same=same)
+        out = autodiff.AdvectDifferentialCentered.apply(meta, *([src] if same else [_expand(src, B), _expand(vel, B)]))
+    else:
+        out = be.empty((B,) + tuple(src.shape[1:]), u.dtype)
+        be.ctx.advect_differential_centered(grid, src.data_ptr(), u.batch_size, s_codes, s_val, vel.data_ptr(), velocity.batch_size, out.data_ptr(), be.stream())
+    return Field(velocity.resolution, velocity.bounds, velocity.boundary, out, False, be, batched, vector=True)
+
+
+finite_difference = differential
 
 
 def mac_cormack(field: Field, velocity: Field, dt: float, correction_strength=1.0, integrator: Callable = euler) -> Field:

@@ -300,6 +300,98 @@ class GradientCentered(torch.autograd.Function):
         return None, gin
 
 
+class GradientFaces(torch.autograd.Function):
+    """ spatial_gradient(at='face') of a centred scalar: (batch, *res) -> one tensor per stored face component. Linear; its transpose is the negative
+    staggered divergence with zero walls (a face that is not stored receives nothing), which the divergence kernel computes on meta['grid_zero']. """
+
+    @staticmethod
+    def forward(ctx, meta, p):
+        be = meta['be']
+        comps = [be.zeros(shape, p.dtype) for shape in meta['shapes']]
+        be.ctx.grad_subtract(meta['grid'], 0, 1, p.contiguous().data_ptr(), _ptrs(comps), be.stream())
+        ctx.meta = meta
+        ctx.shape = tuple(p.shape)
+        return tuple(-c for c in comps)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        meta = ctx.meta
+        be = meta['be']
+        g = [gi.contiguous() if gi is not None else be.zeros(shape, meta['dtype']) for gi, shape in zip(grads, meta['shapes'])]
+        div = be.empty(ctx.shape, meta['dtype'])
+        be.ctx.divergence(meta['grid_zero'], _ptrs(g), 0, 1, False, div.data_ptr(), be.stream())
+        return None, -div
+
+
+class AdvectDifferentialStaggered(torch.autograd.Function):
+    """ -(velocity . grad) u on the stored faces (csrc/momentum.hpp). meta['same']: u IS the velocity -- one set of D tensors comes in and its gradient is
+    the sum of the gradient w.r.t. u and the gradient w.r.t. the velocity. Otherwise the inputs are u's D components followed by the velocity's. """
+
+    @staticmethod
+    def forward(ctx, meta, *tensors):
+        D = meta['rank']
+        t = [x.contiguous() for x in tensors]
+        u, vel = (t, t) if meta['same'] else (t[:D], t[D:])
+        be = meta['be']
+        out = [be.empty(tuple(x.shape), x.dtype) for x in u]
+        B = u[0].shape[0]
+        be.ctx.advect_differential(meta['grid'], _ptrs(u), B, _ptrs(vel), B, _ptrs(out), be.stream())
+        ctx.meta = meta
+        ctx.save_for_backward(*t)
+        return tuple(out)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        meta = ctx.meta
+        be = meta['be']
+        D = meta['rank']
+        t = list(ctx.saved_tensors)
+        u, vel = (t, t) if meta['same'] else (t[:D], t[D:])
+        g = [gi.contiguous() if gi is not None else torch.zeros_like(x) for gi, x in zip(grads, u)]
+        need = ctx.needs_input_grad[1:]
+        want_u = meta['same'] or any(need[:D])
+        want_v = meta['same'] or any(need[D:])
+        gu = [torch.zeros_like(x) for x in u] if want_u else None
+        gv = [torch.zeros_like(x) for x in vel] if want_v else None
+        be.ctx.advect_differential_backward(meta['grid'], _ptrs(u), _ptrs(vel), _ptrs(g), _ptrs(gu) if gu else None, _ptrs(gv) if gv else None, be.stream())
+        if meta['same']:
+            return (None, *[a + b for a, b in zip(gu, gv)])
+        none = [None] * D
+        return (None, *(gu or none), *(gv or none))
+
+
+class AdvectDifferentialCentered(torch.autograd.Function):
+    """ the centred form: u, velocity (batch, D, *res); meta['same'] as in AdvectDifferentialStaggered """
+
+    @staticmethod
+    def forward(ctx, meta, *tensors):
+        t = [x.contiguous() for x in tensors]
+        u, vel = (t[0], t[0]) if meta['same'] else t
+        be = meta['be']
+        out = be.empty(tuple(u.shape), u.dtype)
+        B = u.shape[0]
+        be.ctx.advect_differential_centered(meta['grid'], u.data_ptr(), B, meta['s_codes'], meta['s_val'], vel.data_ptr(), B, out.data_ptr(), be.stream())
+        ctx.meta = meta
+        ctx.save_for_backward(*t)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        meta = ctx.meta
+        be = meta['be']
+        t = list(ctx.saved_tensors)
+        u, vel = (t[0], t[0]) if meta['same'] else t
+        g = grad.contiguous()
+        need = ctx.needs_input_grad[1:]
+        gu = torch.zeros_like(u) if meta['same'] or need[0] else None
+        gv = torch.zeros_like(vel) if meta['same'] or need[1] else None
+        be.ctx.advect_differential_centered_backward(meta['grid'], u.data_ptr(), meta['s_codes'], meta['s_val'], vel.data_ptr(), g.data_ptr(),
+                                                     gu.data_ptr() if gu is not None else 0, gv.data_ptr() if gv is not None else 0, be.stream())
+        if meta['same']:
+            return None, gu + gv
+        return None, gu, gv
+
+
 class DivergenceCentered(torch.autograd.Function):
     """ (batch, D, *res) -> (batch, *res) """
 

@@ -1413,4 +1413,69 @@ int phihip_curl_2d_backward(phihip_ctx* ctx, const phihip_grid* grid, int stagge
     return run_curl2d(ctx, v, staggered, s_bc, nullptr, 1, grad_out, nullptr, grad_vx, b, s);
 }
 
+// ---- the finite-difference advection term (momentum.hpp) ---------------------------------------------------------------------------------------
+int phihip_advect_differential(phihip_ctx* ctx, const phihip_grid* grid, const void* const u[3], int u_batch, const void* const velocity[3], int velocity_batch,
+                               void* const out[3], void* stream) {
+    PHIHIP_ENTER(ctx, grid);
+    PHIHIP_TRY(check_ptrs(v, u, "u"));
+    PHIHIP_TRY(check_ptrs(v, velocity, "velocity"));
+    PHIHIP_TRY(check_ptrs(v, (const void* const*)out, "out"));
+    PHIHIP_REQUIRE(u_batch == 1 || u_batch == v.batch, "advect_differential: u_batch must be 1 or grid.batch");
+    PHIHIP_REQUIRE(velocity_batch == 1 || velocity_batch == v.batch, "advect_differential: velocity_batch must be 1 or grid.batch");
+    for (int d = 0; d < v.rank; ++d)
+        for (int e = 0; e < v.rank; ++e) PHIHIP_REQUIRE(out[d] != u[e] && out[d] != velocity[e], "advect_differential: out[%d] must not alias an input", d);
+    const void *f[3], *w[3];
+    void* o[3];
+    remap3(v, u, f);
+    remap3(v, velocity, w);
+    remap3w(v, out, o);
+    return run_advect_differential(ctx, v, f, u_batch, w, velocity_batch, o, s);
+}
+
+int phihip_advect_differential_backward(phihip_ctx* ctx, const phihip_grid* grid, const void* const u[3], const void* const velocity[3],
+                                        const void* const grad_out[3], void* const grad_u[3], void* const grad_velocity[3], void* stream) {
+    PHIHIP_ENTER(ctx, grid);
+    PHIHIP_TRY(check_ptrs(v, u, "u"));
+    PHIHIP_TRY(check_ptrs(v, velocity, "velocity"));
+    PHIHIP_TRY(check_ptrs(v, grad_out, "grad_out"));
+    PHIHIP_REQUIRE(grad_u || grad_velocity, "advect_differential_backward: grad_u and grad_velocity are both NULL");
+    if (grad_u) PHIHIP_TRY(check_ptrs(v, (const void* const*)grad_u, "grad_u"));
+    if (grad_velocity) PHIHIP_TRY(check_ptrs(v, (const void* const*)grad_velocity, "grad_velocity"));
+    for (int d = 0; d < v.rank; ++d)
+        for (int e = 0; e < v.rank; ++e) {
+            PHIHIP_REQUIRE(!grad_u || (grad_u[d] != u[e] && grad_u[d] != velocity[e] && grad_u[d] != grad_out[e]), "advect_differential_backward: grad_u[%d] aliases an input", d);
+            PHIHIP_REQUIRE(!grad_velocity || (grad_velocity[d] != u[e] && grad_velocity[d] != velocity[e] && grad_velocity[d] != grad_out[e]),
+                           "advect_differential_backward: grad_velocity[%d] aliases an input", d);
+        }
+    const void *f[3], *w[3], *go[3];
+    void *gu[3], *gv[3];
+    remap3(v, u, f);
+    remap3(v, velocity, w);
+    remap3(v, grad_out, go);
+    remap3w(v, grad_u, gu);
+    remap3w(v, grad_velocity, gv);
+    return run_advect_differential_bwd(ctx, v, f, w, go, grad_u ? gu : nullptr, grad_velocity ? gv : nullptr, s);
+}
+
+int phihip_advect_differential_centered(phihip_ctx* ctx, const phihip_grid* grid, const void* u, int u_batch, const int32_t s_bc[3][2], const double s_val[3][2],
+                                        const void* velocity, int velocity_batch, void* out, void* stream) {
+    PHIHIP_ENTER(ctx, grid);
+    PHIHIP_REQUIRE(u && velocity && out && s_bc && out != u && out != velocity, "advect_differential_centered: NULL or aliased argument");
+    PHIHIP_REQUIRE(u_batch == 1 || u_batch == v.batch, "advect_differential_centered: u_batch must be 1 or grid.batch");
+    PHIHIP_REQUIRE(velocity_batch == 1 || velocity_batch == v.batch, "advect_differential_centered: velocity_batch must be 1 or grid.batch");
+    PHIHIP_TRY(check_scalar_bc(v, s_bc, "advect_differential_centered"));
+    return run_advect_differential_centered(ctx, v, u, u_batch, s_bc, s_val, velocity, velocity_batch, out, s);
+}
+
+int phihip_advect_differential_centered_backward(phihip_ctx* ctx, const phihip_grid* grid, const void* u, const int32_t s_bc[3][2], const double s_val[3][2],
+                                                 const void* velocity, const void* grad_out, void* grad_u, void* grad_velocity, void* stream) {
+    PHIHIP_ENTER(ctx, grid);
+    PHIHIP_REQUIRE(u && velocity && grad_out && s_bc && (grad_u || grad_velocity), "advect_differential_centered_backward: NULL argument");
+    PHIHIP_REQUIRE(grad_u != u && grad_u != velocity && grad_u != grad_out && grad_velocity != u && grad_velocity != velocity && grad_velocity != grad_out &&
+                       (grad_u != grad_velocity || !grad_u),
+                   "advect_differential_centered_backward: a gradient aliases an input or the other gradient");
+    PHIHIP_TRY(check_scalar_bc(v, s_bc, "advect_differential_centered_backward"));
+    return run_advect_differential_centered_bwd(ctx, v, u, s_bc, s_val, velocity, grad_out, grad_u, grad_velocity, s);
+}
+
 }  // extern "C"

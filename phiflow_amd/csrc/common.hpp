@@ -405,6 +405,14 @@ int run_cgrad(phihip_ctx*, const GridView&, const void* in, const int32_t s_bc[3
 int run_cdiv(phihip_ctx*, const GridView&, const void* in, const int32_t s_bc[3][2], const double s_val[3][2], void* out, int adjoint, hipStream_t);
 int run_curl2d(phihip_ctx*, const GridView&, int staggered, const int32_t s_bc[3][2], const double s_val[3][2], int adjoint, const void* a, const void* b,
                void* oa, void* ob, hipStream_t);
+// the finite-difference advection term (momentum.hpp, compiled through project.hip); the *_bwd gradients accumulate, a NULL gradient is skipped
+int run_advect_differential(phihip_ctx*, const GridView&, const void* const u[3], int u_batch, const void* const vel[3], int vel_batch, void* const out[3], hipStream_t);
+int run_advect_differential_bwd(phihip_ctx*, const GridView&, const void* const u[3], const void* const vel[3], const void* const gout[3], void* const gu[3],
+                                void* const gv[3], hipStream_t);
+int run_advect_differential_centered(phihip_ctx*, const GridView&, const void* u, int u_batch, const int32_t s_bc[3][2], const double s_val[3][2], const void* vel,
+                                     int vel_batch, void* out, hipStream_t);
+int run_advect_differential_centered_bwd(phihip_ctx*, const GridView&, const void* u, const int32_t s_bc[3][2], const double s_val[3][2], const void* vel,
+                                         const void* gout, void* gu, void* gv, hipStream_t);
 int run_laplace_apply(phihip_ctx*, const GridView&, const uint8_t* flags, int mask_batch, const void* p, void* out, hipStream_t);
 int run_laplace_apply_multi(phihip_ctx*, const GridView* lattices, int count, const void* const* in, void* const* out, hipStream_t);   // MODE_APPLY, no flags: lattices of one tile configuration share a launch
 // host scaffolding of the CG drivers (cg.hip; diffuse_coef.hpp reaches it from project.hip's translation unit)

@@ -1780,3 +1780,4 @@ int run_diffuse_implicit_centered(phihip_ctx* ctx, const GridView& v, const void
 }  // namespace phihip
 
 #include "diffops.hpp"
+#include "momentum.hpp"

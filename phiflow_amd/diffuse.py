@@ -172,6 +172,33 @@ def _explicit_coef(u: Field, coef: Optional[Field], factors: List[float], dt: fl
     return u.with_values(cur)
 
 
+def differential(u: Field, diffusivity, gradient=None, order: int = 2, implicit=None, upwind=None, correct_skew=True) -> Field:
+    """ The differential diffusion term d * laplace(u) as it stands on the right-hand side of a PDE (`diffuse.differential`,
+    phi/physics/diffuse.py:98-144), order 2. A number -- and for centred fields a per-axis `vec(...)` / tuple -- gives `laplace(u, weights=diffusivity)`
+    (the same kernels, the same bits); a centred `Field` diffusivity on a centred `u` the conservative flux form of :129-136, through the operator
+    I + L of `diffuse.explicit` with dt = 1 (the term is `explicit(u, d, 1) - u`: one extra rounding of |u + L u| per sample). The result keeps u's
+    sample layout and carries `u.boundary - u.boundary` (:141): PERIODIC and ZERO_GRADIENT stay, a constant becomes ZERO. Differentiable w.r.t. u.
+    `gradient`, `upwind` and `correct_skew` belong to the reference's mesh branch and are not read. """
+    from .field import _difference_extrapolation, _laplace_on_lattice, require_plain
+    require_plain(u, 'diffuse.differential')
+    if order != 2:
+        raise NotImplementedError("HIP backend: diffuse.differential implements order=2 only")
+    if implicit is not None:
+        raise NotImplementedError("HIP backend: diffuse.differential computes the explicit stencil only; pass implicit=None (diffuse.implicit solves)")
+    ext = _difference_extrapolation(u.boundary, u.dims)
+    coef, k = _diffusivity(u, diffusivity, 'diffuse.differential')
+    if coef is not None:
+        with warnings.catch_warnings():         # (dt = 1 is no time step: the CFL warning of diffuse.explicit does not apply to a right-hand side)
+            warnings.simplefilter('ignore', RuntimeWarning)
+            lap = explicit(u, diffusivity, 1.0) - u
+    else:
+        lap = _laplace_on_lattice(u, None, tuple(k) if isinstance(k, list) else k, 2)
+    return Field(u.resolution, u.bounds, ext, lap.values, u.is_staggered, u.backend, lap.batched, vector=u.is_vector)
+
+
+finite_difference = differential
+
+
 def implicit(field: Field, diffusivity, dt: float, solve=None, order: int = 2) -> Field:
     """ Implicit Euler diffusion (`diffuse.implicit`, phi/physics/diffuse.py:63-92; Heat_Flow.ipynb, Burgers.ipynb): solves
     `(1 - diffusivity * dt * laplace) u = field` with CG from `x0 = field` -- `solve_linear(sharpen, y=field, solve)` with

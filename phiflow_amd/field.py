@@ -257,6 +257,16 @@ class Field:
     def divergence(self, order: int = 2) -> 'Field':
         return divergence(self, order)
 
+    def gradient(self, boundary=None, at: str = 'center', order: int = 2) -> 'Field':
+        """ `field.gradient(boundary, at, order)` (phi/field/_field.py `Field.gradient`): `spatial_gradient` as a method, with the reference's default location
+        'center' (the function's default here stays 'face') """
+        return spatial_gradient(self, boundary, at=at, order=order)
+
+    @property
+    def sampled_at(self) -> str:
+        """ 'face' for a StaggeredGrid, 'center' for a CenteredGrid (phi/field/_field.py `Field.sampled_at`) """
+        return 'face' if self.is_staggered else 'center'
+
     def curl(self, at: str = 'corner') -> 'Field':
         return curl(self, at)
 
@@ -547,6 +557,13 @@ def spatial_gradient(field: Field, boundary=None, at: str = 'face', order: int =
     grid = _capi.make_grid(field.spatial_rank, _torch_dtype_code(field.dtype), field.batch_size, list(field.resolution.values()),
                            field.bounds.lower, field.bounds.upper, proto._codes, proto._bc_val)
     _check_pressure_padding(field.boundary, vb, field.dims)
+    from . import autodiff
+    if autodiff.needs_grad(field.values):
+        shapes = [(field.batch_size,) + component_shape(field.resolution, vb, d) for d in range(field.spatial_rank)]
+        grid_zero = _capi.make_grid(field.spatial_rank, _torch_dtype_code(field.dtype), field.batch_size, list(field.resolution.values()),
+                                    field.bounds.lower, field.bounds.upper, proto._codes)
+        meta = dict(be=be, grid=grid, grid_zero=grid_zero, shapes=shapes, dtype=field.dtype)
+        return Field(field.resolution, field.bounds, vb, list(autodiff.GradientFaces.apply(meta, field.values)), True, be, field.batched)
     comps = [be.zeros((field.batch_size,) + component_shape(field.resolution, vb, d), field.dtype) for d in range(field.spatial_rank)]
     be.ctx.grad_subtract(grid, 0, 1, field.values.contiguous().data_ptr(), _ptrs(comps), be.stream())
     comps = [-c for c in comps]
@@ -620,12 +637,18 @@ def laplace(u: Field, axes=None, weights=None, order: int = 2) -> Field:
     centred vector field, every component of a StaggeredGrid on its own faces with that component's wall constant -- U being the field padded
     with its own extrapolation. Result: the same kind of field with `u.extrapolation.spatial_gradient().spatial_gradient()`.
     Per-axis weights and axis subsets are for centred fields. Differentiable w.r.t. u. """
+    out = _laplace_on_lattice(u, axes, weights, order)
+    # (a staggered result re-stores its faces: BOUNDARY -> ZERO drops the outer ones, _field_math.py:145)
+    return out.with_boundary(u.boundary.spatial_gradient().spatial_gradient())
+
+
+def _laplace_on_lattice(u: Field, axes, weights, order: int) -> Field:
+    """ the values of `laplace` as a field with u's OWN boundary and sample layout (`laplace` and `diffuse.differential` give it their extrapolation) """
     from . import autodiff
     require_plain(u, 'laplace')
     if order != 2:
         raise NotImplementedError("HIP backend: laplace implements order=2 only")
     w = _laplace_weights(u, axes, weights)
-    lap_ext = u.boundary.spatial_gradient().spatial_gradient()
     be = u.backend
     if u.is_staggered:
         if any(k != w[0] for k in w):
@@ -636,7 +659,7 @@ def laplace(u: Field, axes=None, weights=None, order: int = 2) -> Field:
         else:
             out = [be.empty(tuple(t.shape), u.dtype) for t in vals]
             be.ctx.field_laplace(u.grid_struct(), _ptrs(vals), _ptrs(out), w[0], False, be.stream())
-        return u.with_values(out).with_boundary(lap_ext)        # (re-stores the faces: BOUNDARY -> ZERO drops the outer ones, _field_math.py:145)
+        return u.with_values(out)
     _check_diff_rank(u, 'laplace')
     if u.is_vector:
         require_scalar_boundary(u.boundary, u.dims, 'laplace')
@@ -649,7 +672,7 @@ def laplace(u: Field, axes=None, weights=None, order: int = 2) -> Field:
     else:
         out = be.empty(tuple(folded.shape), u.dtype)
         be.ctx.field_laplace_centered(meta['grid'], folded.data_ptr(), s_codes, s_val, w, out.data_ptr(), False, be.stream())
-    return Field(u.resolution, u.bounds, lap_ext, out.reshape(src.shape), False, be, u.batched, vector=u.is_vector)
+    return Field(u.resolution, u.bounds, u.boundary, out.reshape(src.shape), False, be, u.batched, vector=u.is_vector)
 
 
 def _gradient_centered(s: Field, boundary) -> Field:

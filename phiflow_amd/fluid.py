@@ -302,6 +302,66 @@ def make_incompressible(velocity: Field,
     return v_out, p_out
 
 
+def incompressible_rk4(pde, velocity: Field, pressure: Field, dt, pressure_order=4, pressure_solve: Solve = Solve('CG'), **pde_aux_kwargs):
+    """
+    The 4th-order Runge-Kutta time step for incompressible vector fields that carries the pressure through the stages
+    (phi/physics/fluid.py:291-334, after Kampanis et al. 2006), restated line for line.
+
+    Args:
+        pde: momentum equation: computes every term that is not the pressure's, e.g. `lambda v: advect.differential(v, v) + diffuse.differential(v, nu)`.
+        velocity: `StaggeredGrid` at time t whose every side is PERIODIC or a zero wall.
+        pressure: `CenteredGrid` at time t with the pressure's extrapolation (PERIODIC / ZERO_GRADIENT at walls).
+        dt: time increment.
+        pressure_order: only 2 is implemented. The reference's default 4 stays the default and is refused: pass `pressure_order=2`.
+        pressure_solve: `Solve` of the four projections.
+        **pde_aux_kwargs: constant arguments of `pde`.
+
+    Returns:
+        velocity and pressure at time t + dt.
+    """
+    from .extrapolation import ConstantExtrapolation, _Boundary
+    if pressure_order != 2:
+        raise NotImplementedError(f"HIP backend: incompressible_rk4 implements pressure_order=2 only (got {pressure_order}; the reference's default is 4 and "
+                                  f"would give other numbers): pass pressure_order=2")
+    if not velocity.is_staggered:
+        raise NotImplementedError("HIP backend: incompressible_rk4 of a CenteredGrid velocity is not implemented; pass a StaggeredGrid (`StaggeredGrid(v, ...)`)")
+    if pde_aux_kwargs.get('obstacles'):
+        raise NotImplementedError("HIP backend: incompressible_rk4 with obstacles is not implemented (the stage projections do not see them); use the split "
+                                  "step with make_incompressible(v, obstacles)")
+    for d in velocity.dims:
+        for upper in (False, True):
+            side = velocity.boundary.side(d, upper)
+            if isinstance(side, _Boundary):
+                raise NotImplementedError(f"HIP backend: incompressible_rk4 with an OPEN (zero-gradient) side {d}{'+' if upper else '-'} is not implemented (the "
+                                          f"pressure gradient has another face layout there); use PERIODIC or zero walls, or the split step")
+            if isinstance(side, ConstantExtrapolation) and any(side.component_value(c, n) != 0 for c, n in enumerate(velocity.dims)):
+                raise NotImplementedError(f"HIP backend: incompressible_rk4 with a non-zero wall constant ({side} on side {d}{'+' if upper else '-'}) is not "
+                                          f"implemented (`v + dt * rhs` keeps the left operand's boundary here); use zero walls or PERIODIC, or the split step")
+    v1, p1 = velocity, pressure
+    # PDE at current point
+    rhs1 = pde(v1, **pde_aux_kwargs) - p1.gradient(at=v1.sampled_at, order=pressure_order)
+    v2_old = velocity + (dt / 2) * rhs1
+    v2, delta_p = make_incompressible(v2_old, solve=pressure_solve, order=pressure_order)
+    p2 = p1 + delta_p / dt
+    # PDE at half-point
+    rhs2 = pde(v2, **pde_aux_kwargs) - p2.gradient(at=v1.sampled_at, order=pressure_order)
+    v3_old = velocity + (dt / 2) * rhs2
+    v3, delta_p = make_incompressible(v3_old, solve=pressure_solve, order=pressure_order)
+    p3 = p2 + delta_p / dt
+    # PDE at corrected half-point
+    rhs3 = pde(v3, **pde_aux_kwargs) - p3.gradient(at=v1.sampled_at, order=pressure_order)
+    v4_old = velocity + dt * rhs2
+    v4, delta_p = make_incompressible(v4_old, solve=pressure_solve, order=pressure_order)
+    p4 = p3 + delta_p / dt
+    # PDE at RK4 point
+    rhs4 = pde(v4, **pde_aux_kwargs) - p4.gradient(at=v1.sampled_at, order=pressure_order)
+    v_p1_old = velocity + (dt / 6) * (rhs1 + 2 * rhs2 + 2 * rhs3 + rhs4)
+    p_p1_old = (1 / 6) * (p1 + 2 * p2 + 2 * p3 + p4)
+    v_p1, delta_p = make_incompressible(v_p1_old, solve=pressure_solve, order=pressure_order)
+    p_p1 = p_p1_old + delta_p / dt
+    return v_p1, p_p1
+
+
 def _require_staggered_velocity(velocity: Field, what: str):
     """ obstacles meet staggered velocities only: the kernels take one array per face component """
     if not velocity.is_staggered:
