@@ -15,7 +15,10 @@ constexpr int kVmax = 16 / sizeof(InstT);
 
 template <int V, int R, int TPR, int MODE, bool FLAGS, bool UNAL = false, bool ROWT = false>
 static void launch_one(const MarchGrid& g, const MarchArgs<InstT>& a, dim3 grid, hipStream_t s) {
-    if constexpr (UNAL || ROWT) {      // rows that are not whole vectors / unaligned buffers, and the row tile (stencil_march.hpp): one marching direction
+    if constexpr (UNAL) {      // rows that are not whole vectors (RAG: they end in an overlapping vector) / unaligned buffers: one marching direction
+        if (g.n2 % V != 0) hipLaunchKernelGGL((march_kernel<InstT, V, R, TPR, MODE, FLAGS, kInstDim3, false, true, false, true>), grid, dim3(kBlock), 0, s, g, a);
+        else hipLaunchKernelGGL((march_kernel<InstT, V, R, TPR, MODE, FLAGS, kInstDim3, false, true, false, false>), grid, dim3(kBlock), 0, s, g, a);
+    } else if constexpr (ROWT) {      // the row tile (stencil_march.hpp): one marching direction
         hipLaunchKernelGGL((march_kernel<InstT, V, R, TPR, MODE, FLAGS, kInstDim3, false, UNAL, ROWT>), grid, dim3(kBlock), 0, s, g, a);
     } else {
         // the bidirectional variant exists for 3-D MATVEC and UPDATE_R (the 3-word phases: the stencil source's halo planes weigh most there)
@@ -202,7 +205,13 @@ int launch_march_multi<InstT, kInstDim3>(const MarchConfig& c, int count, const 
     }
     dim3 grid(nblk, c.batch, count);
     if (c.vec == 1) return launch_multi_cfg<1, 1, 64>(m, a, grid, s);
-    if (c.vec < 0) return launch_multi_cfg<kVmax, 1, 64, true>(m, a, grid, s);
+    if (c.vec < 0) {      // (RAG as soon as one lattice's rows end in an overlapping vector)
+        bool rag = false;
+        for (int l = 0; l < count; ++l) rag = rag || g[l].n2 % kVmax != 0;
+        if (rag) hipLaunchKernelGGL((march_apply_multi_kernel<InstT, kVmax, 1, 64, kInstDim3, true, false, true>), grid, dim3(kBlock), 0, s, m, a);
+        else hipLaunchKernelGGL((march_apply_multi_kernel<InstT, kVmax, 1, 64, kInstDim3, true, false, false>), grid, dim3(kBlock), 0, s, m, a);
+        return PHIHIP_OK;
+    }
     if (c.vec == 2 && kVmax == 4) {
         switch (c.id) {
             case 4: return launch_multi_cfg<(kVmax == 4 ? 2 : kVmax), 4, 64>(m, a, grid, s);

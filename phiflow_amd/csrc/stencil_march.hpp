@@ -238,7 +238,8 @@ __device__ __forceinline__ void vec_store(T* p, const Vec<T, V>& x) {
 // ---- rows that are not whole 16-byte vectors / buffers that are not 16-byte aligned (UNAL instantiation of march_kernel, r4) -----------------
 // Global accesses take the vector at ELEMENT alignment (gfx950 serves dwordx4 at any 4-byte address), and the thread that would own the
 // partial vector at the end of a row owns the row's LAST V cells instead: its vector overlaps its left neighbour's by V - (n2 mod V) cells,
-// both compute the same bits for those cells from the same operands and store them twice, only the sums count them once. No element is
+// both compute the same bits for those cells from the same operands (the RAG instantiation: in ONE rounding sequence, see mul_unfused) and store them twice, only the
+// sums count them once. No element is
 // rotated or masked in registers (a first version that loaded the partial vector early and rotated it with selects was turned into a
 // dynamically indexed array in SCRATCH by the compiler: 80-270 bytes per lane), no byte outside the arrays is touched.
 template <typename T, int V>
@@ -261,6 +262,17 @@ __device__ __forceinline__ void vec_store_g(T* p, const Vec<T, V>& x) {
 #pragma unroll
     for (int i = 0; i < V; ++i) t.v[i] = x.v[i];
     *reinterpret_cast<VecP<T, V>*>(p) = t;
+}
+// A cell of the overlap is computed by TWO threads, at different positions v of their vectors, and whichever store lands last stays, while the neighbour alone counts
+// it. hipcc's default contraction fuses a multiply with a neighbouring addition per position as it sees fit: on the MI355X the two threads' fp32 results differed in the
+// last bit in one cell of seven (columns 9 ... 11 of a 13-cell row against the same code on a 16-cell row), and the sums held the value that was NOT stored. RAG is the
+// UNAL instantiation for rows that END in an overlapping vector (n2 mod V != 0): every value it stores is formed from differences, explicit fma and this product that
+// cannot fuse -- one rounding sequence whatever the position. Whole-vector rows on unaligned buffers have no overlap and keep UNAL's arithmetic, which is the aligned
+// instantiations' bit for bit.
+template <typename T>
+__device__ __forceinline__ T mul_unfused(T a, T b) {
+#pragma clang fp contract(off)
+    return a * b;
 }
 // LDS copy of the tile: vectors sit on 16-byte boundaries except the overlapping last vector of a ragged row (`odd`: element by element)
 template <typename T, int V>
@@ -392,7 +404,7 @@ constexpr int march_min_waves() {
 // the mid-size dip is made of (1.49 fabric read requests per needed one at 320^3 against 1.13 at 512^3).
 // march_body: the kernel's body as a device function (r6), so that TWO entry points share it -- march_kernel (one lattice per launch: every CG phase) and
 // march_apply_multi_kernel (MODE_APPLY on up to three lattices in ONE launch: the components of diffuse.explicit, phi/physics/diffuse.py:13-60 is one call).
-template <typename T, int V, int R, int TPR, int MODE, bool FLAGS, bool DIM3, bool BIDIR = false, bool UNAL = false, bool ROWT = false>
+template <typename T, int V, int R, int TPR, int MODE, bool FLAGS, bool DIM3, bool BIDIR = false, bool UNAL = false, bool ROWT = false, bool RAG = false>
 __device__ __forceinline__ void march_body(const MarchGrid& g, const MarchArgs<T>& p) {
     constexpr int TRc = ROWT ? kBlock / (TPR / 2 + 1) : kBlock / TPR;   // thread rows (ROWT: at most -- rows of more than TPR / 2 lanes)
     constexpr int T1c = TRc * R;       // tile rows (axis a1)
@@ -404,6 +416,7 @@ __device__ __forceinline__ void march_body(const MarchGrid& g, const MarchArgs<T
     constexpr bool WIDE = ROWT && TPR > 128;
     static_assert(ROWT || 2 * TPR + 2 * T1c <= kBlock, "halo items must fit one per thread");
     static_assert(!(ROWT && (UNAL || BIDIR)), "the row tile exists for aligned rows and one marching direction");
+    static_assert(!RAG || UNAL, "RAG is the UNAL instantiation for rows that END in an overlapping vector");
     const int tpr = ROWT ? g.tpr_rt : TPR;                      // lanes per row
     const int T1 = ROWT ? (kBlock / tpr) * R : T1c;
     const int T2 = ROWT ? g.n2 : T2c;
@@ -755,7 +768,27 @@ __device__ __forceinline__ void march_body(const MarchGrid& g, const MarchArgs<T
                 const T lo2 = v > 0 ? Sc[rr].v[v > 0 ? v - 1 : 0] : lf;
                 const T hi2 = v < V - 1 ? Sc[rr].v[v < V - 1 ? v + 1 : v] : rt;
                 T r;
-                if (FLAGS) {
+                if (RAG) {      // the same stencils in ONE rounding sequence for every position v (see mul_unfused)
+                    if (FLAGS) {
+                        const unsigned f = Ec.fl[rr].v[v];
+                        r = T(0);
+                        if (DIM3) {
+                            if (f & bit_behind) r = fma(Sp[rr].v[v] - c, p.w0, r);
+                            if (f & bit_ahead) r = fma(Sn[rr].v[v] - c, p.w0, r);
+                        }
+                        if (f & 4u) r = fma(up.v[v] - c, p.w1, r);
+                        if (f & 8u) r = fma(dn.v[v] - c, p.w1, r);
+                        if (f & 16u) r = fma(lo2 - c, p.w2, r);
+                        if (f & 32u) r = fma(hi2 - c, p.w2, r);
+                        r = fma(p.ident, c, r);
+                        if (!(f & 64u)) r = c;
+                    } else {
+                        r = mul_unfused((dn.v[v] - c) - (c - up.v[v]), p.w1);
+                        if (DIM3) r = fma((Sn[rr].v[v] - c) - (c - Sp[rr].v[v]), p.w0, r);
+                        r = fma((hi2 - c) - (c - lo2), p.w2, r);
+                        r = fma(p.ident, c, r);
+                    }
+                } else if (FLAGS) {
                     const unsigned f = Ec.fl[rr].v[v];
                     r = T(0);
                     if (DIM3) {
@@ -855,9 +888,15 @@ __device__ __forceinline__ void march_body(const MarchGrid& g, const MarchArgs<T
                 VT xn, rn;
 #pragma unroll
                 for (int v = 0; v < V; ++v) {
-                    if (MODE == MODE_UPDATE_X2) xn.v[v] = Ec.e1[rr].v[v] + beta * (Sc[rr].v[v] - Ec.e2[rr].v[v]) + alpha * Sc[rr].v[v];
-                    else if (HAS_X) xn.v[v] = Ec.e1[rr].v[v] + alpha * Sc[rr].v[v];
-                    rn.v[v] = Ec.e2[rr].v[v] - alpha * q.v[v];
+                    if (RAG) {      // (one rounding sequence for every position v, see mul_unfused)
+                        if (MODE == MODE_UPDATE_X2) xn.v[v] = fma(alpha, Sc[rr].v[v], fma(beta, Sc[rr].v[v] - Ec.e2[rr].v[v], Ec.e1[rr].v[v]));
+                        else if (HAS_X) xn.v[v] = fma(alpha, Sc[rr].v[v], Ec.e1[rr].v[v]);
+                        rn.v[v] = fma(-alpha, q.v[v], Ec.e2[rr].v[v]);
+                    } else {
+                        if (MODE == MODE_UPDATE_X2) xn.v[v] = Ec.e1[rr].v[v] + beta * (Sc[rr].v[v] - Ec.e2[rr].v[v]) + alpha * Sc[rr].v[v];
+                        else if (HAS_X) xn.v[v] = Ec.e1[rr].v[v] + alpha * Sc[rr].v[v];
+                        rn.v[v] = Ec.e2[rr].v[v] - alpha * q.v[v];
+                    }
                     s1 += once(v, rn.v[v] * rn.v[v]);
                     if (AD) s2 += once(v, rn.v[v] * q.v[v]);
                 }
@@ -899,9 +938,9 @@ __device__ __forceinline__ void march_body(const MarchGrid& g, const MarchArgs<T
     }
 }
 
-template <typename T, int V, int R, int TPR, int MODE, bool FLAGS, bool DIM3, bool BIDIR = false, bool UNAL = false, bool ROWT = false>
+template <typename T, int V, int R, int TPR, int MODE, bool FLAGS, bool DIM3, bool BIDIR = false, bool UNAL = false, bool ROWT = false, bool RAG = false>
 __global__ __launch_bounds__(kBlock, (UNAL ? 1 : march_min_waves<T, R, MODE, FLAGS>())) void march_kernel(MarchGrid g, MarchArgs<T> p) {
-    march_body<T, V, R, TPR, MODE, FLAGS, DIM3, BIDIR, UNAL, ROWT>(g, p);
+    march_body<T, V, R, TPR, MODE, FLAGS, DIM3, BIDIR, UNAL, ROWT, RAG>(g, p);
 }
 
 // MODE_APPLY (out = (ident + sum_a w_a d^2_a) in) on up to three lattices of one tile configuration in ONE launch: blockIdx.z selects the lattice -- its shape,
@@ -913,7 +952,7 @@ struct MarchMulti {
     const T* in[3];
     T* out[3];
 };
-template <typename T, int V, int R, int TPR, bool DIM3, bool UNAL = false, bool ROWT = false>
+template <typename T, int V, int R, int TPR, bool DIM3, bool UNAL = false, bool ROWT = false, bool RAG = false>
 __global__ __launch_bounds__(kBlock, (UNAL ? 1 : march_min_waves<T, R, MODE_APPLY, false>())) void march_apply_multi_kernel(MarchMulti<T> m, MarchArgs<T> p) {
     const int l = blockIdx.z;              // uniform: the lattice's descriptor comes from the kernel arguments with scalar loads
     const MarchGrid g = m.g[l];
@@ -921,7 +960,7 @@ __global__ __launch_bounds__(kBlock, (UNAL ? 1 : march_min_waves<T, R, MODE_APPL
     MarchArgs<T> q = p;
     q.a = m.in[l];
     q.o1 = m.out[l];
-    march_body<T, V, R, TPR, MODE_APPLY, false, DIM3, false, UNAL, ROWT>(g, q);
+    march_body<T, V, R, TPR, MODE_APPLY, false, DIM3, false, UNAL, ROWT, RAG>(g, q);
 }
 
 }  // namespace phihip

@@ -21,6 +21,7 @@ import diffuse_coef_elementwise_cases as dce   # noqa: E402
 import multigrid_elementwise_cases as mgc   # noqa: E402
 import parity_cases as pc            # noqa: E402
 import project_elementwise_cases as pec   # noqa: E402
+import slab_phase_cases as spc       # noqa: E402
 from phiflow_amd import _capi as C   # noqa: E402
 
 
@@ -69,6 +70,9 @@ def main():
         ctx = C.Context(C.load_default_library(), 0)
         mem = pc.TorchMem()
     PER, CLO, OPN = pc.PER, pc.CLO, pc.OPN
+    ranks = [C.Context(ctx.lib, 0) for _ in range(3)]      # the emulated ranks of the slab-decomposed CG phases
+    for c in ranks:
+        c.set_autotune(False)
     fails = 0
     for seed in range(args.first, args.first + args.count):
         r = np.random.default_rng(seed)
@@ -165,6 +169,13 @@ def main():
                 pdx = pec.make_inputs(res, bc, edt, batch).dx
                 for name in ("rotated box", "sphere", "union of three"):
                     pec.check_obstacles(ctx, mem, res, bc, edt, batch, pec.pick_scene(name, res, bc, pdx, seed), "random", seed, what=name)
+            # the slab-decomposed CG phases element by element under the bounds of tests/slab_phase_cases.py: a 3-D grid of its own cut at one or two random
+            # planes, a random slab-axis boundary pair, flags across the cuts or none, in the case's element type
+            step = "slab phases elementwise"
+            sres = (int(r.integers(3, 9)), int(r.integers(3, 7)), int(r.integers(7, 21)))
+            scuts = sorted(int(c) for c in r.choice(np.arange(1, sres[0]), size=int(r.integers(1, 3)), replace=False))
+            sbc = (spc.SLAB_BCS[int(r.integers(0, 3))],) + tuple(spc.KINDS[int(k)] for k in r.integers(0, 5, 2))
+            spc.phases(spc.World(ranks, mem, sres, sbc, dtype, [0] + scuts + [sres[0]], "random", bool(r.integers(0, 2)), seed))
             del pec.RECORDS[:]
             print("ok  ", tag, flush=True)
         except Exception as e:   # noqa: BLE001 -- report and go on
