@@ -184,8 +184,12 @@ int phihip_build_cellflags(phihip_ctx* ctx, const phihip_grid* grid, const uint8
 
 /* ---- f3: obstacles rasterised on the device (phi/physics/fluid.py:130-137, 212-240; phi/geom/_box.py:174-185,217-236;
  *          phi/geom/_sphere.py:107-120; phi/field/_angular_velocity.py:10-47) ------------------------------------------- */
-typedef enum phihip_obstacle_kind { PHIHIP_OBSTACLE_BOX = 0, PHIHIP_OBSTACLE_SPHERE = 1, PHIHIP_OBSTACLE_SDF = 2 /* f13, below */ } phihip_obstacle_kind;
-/* Obstacle(geometry, velocity, angular_velocity) with geometry = Box / Cuboid (center, half_size) or Sphere (center, radius) */
+typedef enum phihip_obstacle_kind { PHIHIP_OBSTACLE_BOX = 0, PHIHIP_OBSTACLE_SPHERE = 1, PHIHIP_OBSTACLE_SDF = 2 /* f13, below */,
+                                    PHIHIP_OBSTACLE_CYLINDER = 3 /* f16 */ } phihip_obstacle_kind;
+/* Obstacle(geometry, velocity, angular_velocity) with geometry = Box / Cuboid (center, half_size), Sphere (center, radius) or, rank 3 only,
+ * Cylinder (center, radius, depth, axis, rotation; phi/geom/_cylinder.py:67-92): with local = R^T (x - center), h = local[axis] and r the other
+ * two components, lies_inside = r.r <= radius^2 and |h| <= depth / 2 (inclusive), signed distance = max(|r| - radius, |h| - depth / 2).
+ * A cylinder on a grid of rank 2, with embed_mask != 0, an axis outside 0..2 or a negative radius / depth: PHIHIP_ERR_UNSUPPORTED. */
 typedef struct phihip_obstacle {
     int32_t kind;                 /* phihip_obstacle_kind */
     int32_t group;                /* 0: an obstacle of its own. > 0: CONSECUTIVE entries with the same value form ONE obstacle whose
@@ -195,13 +199,14 @@ typedef struct phihip_obstacle {
     int32_t embed_mask;           /* bit d set: the geometry is infinitely long along axis d (x = bit 0): that coordinate is ignored
                                    * (phi.geom.embed / infinite_cylinder, phi/geom/_embed.py:62-66,139-158). Such obstacles neither
                                    * rotate nor carry a rotation matrix. */
-    int32_t reserved;             /* kind PHIHIP_OBSTACLE_SDF: the slot phihip_sdf_bind returned; otherwise unused */
+    int32_t reserved;             /* kind PHIHIP_OBSTACLE_SDF: the slot phihip_sdf_bind returned; kind PHIHIP_OBSTACLE_CYLINDER: the axis index (0..2, x = 0);
+                                   * otherwise unused */
     double center[3];             /* x, y[, z] */
-    double half_size[3];          /* box: half extents; sphere: half_size[0] = radius */
+    double half_size[3];          /* box: half extents; sphere: half_size[0] = radius; cylinder: [0] = radius, [1] = depth / 2, [2] = 0 */
     double velocity[3];           /* linear velocity of the obstacle */
     double angular_velocity[3];   /* rank 2: [0] = scalar rotation speed; rank 3: rotation vector */
-    double rotation[9];           /* box orientation: row-major matrix R (box frame -> world), local = R^T (x - center)
-                                   * (Box.rotated, phi/geom/_box.py:127-152); all zero = identity */
+    double rotation[9];           /* box / cylinder orientation: row-major matrix R (body frame -> world), local = R^T (x - center)
+                                   * (Box.rotated, phi/geom/_box.py:127-152; phi/geom/_cylinder.py:68); all zero = identity */
 } phihip_obstacle;
 /* accessible[cell] = 1 unless the cell centre lies inside any obstacle (`~union(geometries)` sampled at the centres,
  * fluid.py:133); feed it to phihip_build_cellflags. `obstacles` is a HOST array; accessible is a device uint8 array [cells]. */
@@ -239,7 +244,7 @@ typedef struct phihip_sdf_grid {
 /* copies the description into a free slot of the context and returns its number in *slot */
 int phihip_sdf_bind(phihip_ctx* ctx, const phihip_sdf_grid* desc, int32_t* slot);
 int phihip_sdf_release(phihip_ctx* ctx, int32_t slot);
-/* sample_sdf (phi/geom/_sdf_grid.py:245-298): out[cell] = min over the `count` analytic obstacles (kind BOX / SPHERE; rotation, embed_mask
+/* sample_sdf (phi/geom/_sdf_grid.py:245-298): out[cell] = min over the `count` analytic obstacles (kind BOX / SPHERE / CYLINDER; rotation, embed_mask
  * honoured; group ignored: the list is ONE union) of approximate_signed_distance at the centres of the cells of desc (res, lower, upper,
  * dtype, rank; desc->sdf is ignored). out: DEVICE array [res...] of desc->dtype. */
 int phihip_sdf_from_analytic(phihip_ctx* ctx, const phihip_sdf_grid* desc, const phihip_obstacle* obstacles, int count, void* out, void* stream);

@@ -67,7 +67,7 @@ class ObstacleStruct(ctypes.Structure):
                 ("velocity", c_double * 3), ("angular_velocity", c_double * 3), ("rotation", c_double * 9)]
 
 
-OBSTACLE_BOX, OBSTACLE_SPHERE, OBSTACLE_SDF = 0, 1, 2
+OBSTACLE_BOX, OBSTACLE_SPHERE, OBSTACLE_SDF, OBSTACLE_CYLINDER = 0, 1, 2, 3
 SDF_SLOTS = 64
 
 
@@ -94,7 +94,7 @@ def make_obstacles(items) -> "ctypes.Array":
         arr[k].kind = int(it["kind"])
         arr[k].group = int(it.get("group", 0))
         arr[k].embed_mask = int(it.get("embed_mask", 0))
-        arr[k].reserved = int(it.get("slot", 0))      # kind OBSTACLE_SDF: the slot of Context.sdf_bind
+        arr[k].reserved = int(it.get("slot", it.get("axis", 0)))      # kind OBSTACLE_SDF: the slot of Context.sdf_bind; OBSTACLE_CYLINDER: the axis index
         for d, val in enumerate(it.get("center", ())):
             arr[k].center[d] = float(val)
         for d, val in enumerate(it.get("half_size", ())):

@@ -613,9 +613,20 @@ static int check_obstacles(const phihip_ctx* ctx, const GridView& v, const phihi
             }
             continue;
         }
-        PHIHIP_REQUIRE(obstacles[k].kind == PHIHIP_OBSTACLE_BOX || obstacles[k].kind == PHIHIP_OBSTACLE_SPHERE, "obstacle %d: unknown kind %d", k,
-                       obstacles[k].kind);
-        const int nh = obstacles[k].kind == PHIHIP_OBSTACLE_SPHERE ? 1 : v.rank;
+        PHIHIP_REQUIRE(obstacles[k].kind == PHIHIP_OBSTACLE_BOX || obstacles[k].kind == PHIHIP_OBSTACLE_SPHERE || obstacles[k].kind == PHIHIP_OBSTACLE_CYLINDER,
+                       "obstacle %d: unknown kind %d", k, obstacles[k].kind);
+        if (obstacles[k].kind == PHIHIP_OBSTACLE_CYLINDER) {      // f16: half_size = (radius, depth / 2, 0), reserved = the axis; group, velocities, rotation as for a box
+            const phihip_obstacle& o = obstacles[k];
+            const bool axis_ok = o.reserved >= 0 && o.reserved <= 2;
+            if (v.rank != 3 || o.embed_mask != 0 || !axis_ok || !(o.half_size[0] >= 0) || !(o.half_size[1] >= 0)) {
+                if (v.rank != 3) set_error("obstacle %d: a cylinder needs a grid of rank 3 (got %d; rank 2: a box, or a sphere for the disc)", k, v.rank);
+                else if (o.embed_mask != 0) set_error("obstacle %d: a cylinder cannot be embedded (embed_mask != 0)", k);
+                else if (!axis_ok) set_error("obstacle %d: cylinder axis %d (reserved) must be 0, 1 or 2", k, o.reserved);
+                else set_error("obstacle %d: negative cylinder radius or depth", k);
+                return PHIHIP_ERR_UNSUPPORTED;
+            }
+        }
+        const int nh = obstacles[k].kind == PHIHIP_OBSTACLE_SPHERE ? 1 : (obstacles[k].kind == PHIHIP_OBSTACLE_CYLINDER ? 2 : v.rank);
         for (int d = 0; d < nh; ++d) PHIHIP_REQUIRE(obstacles[k].half_size[d] >= 0, "obstacle %d: negative size", k);
         PHIHIP_REQUIRE(obstacles[k].group >= 0, "obstacle %d: group must be >= 0", k);
         PHIHIP_REQUIRE(obstacles[k].embed_mask >= 0 && obstacles[k].embed_mask < (1 << v.rank) - 1, "obstacle %d: embed_mask must leave one axis", k);
@@ -705,8 +716,8 @@ int phihip_sdf_from_analytic(phihip_ctx* ctx, const phihip_sdf_grid* desc, const
     v.rank = desc->rank;
     v.ax0 = 3 - desc->rank;
     for (int k = 0; k < count; ++k)
-        PHIHIP_REQUIRE(obstacles[k].kind == PHIHIP_OBSTACLE_BOX || obstacles[k].kind == PHIHIP_OBSTACLE_SPHERE,
-                       "sdf_from_analytic: obstacle %d: kind %d is not analytic (Box / Sphere)", k, obstacles[k].kind);
+        PHIHIP_REQUIRE(obstacles[k].kind == PHIHIP_OBSTACLE_BOX || obstacles[k].kind == PHIHIP_OBSTACLE_SPHERE || obstacles[k].kind == PHIHIP_OBSTACLE_CYLINDER,
+                       "sdf_from_analytic: obstacle %d: kind %d is not analytic (Box / Sphere / Cylinder)", k, obstacles[k].kind);
     PHIHIP_TRY(check_obstacles(ctx, v, obstacles, count));
     (void)hipSetDevice(ctx->device);
     return run_sdf_from_analytic(ctx, v, *desc, obstacles, count, out, (hipStream_t)stream);

@@ -893,6 +893,7 @@ struct ObstacleSet {
     int rotated[kObstaclesPerLaunch];
     int group[kObstaclesPerLaunch];          // > 0: consecutive entries with the same value are ONE obstacle (union of the members)
     int skip[kObstaclesPerLaunch];           // bit a (internal axis): the geometry is infinite along a (embed): coordinate ignored
+    int axis[kObstaclesPerLaunch];           // f16, cylinder: the internal axis it is aligned with in its own frame; half = (radius, depth / 2, 0)
 };
 
 static ObstacleSet make_obstacle_set(const GridView& v, const phihip_obstacle* obs, int first, int count) {
@@ -933,7 +934,8 @@ static ObstacleSet make_obstacle_set(const GridView& v, const phihip_obstacle* o
                     s.rot[k][a + v.ax0][c + v.ax0] = o.rotation[a * 3 + c];
                     identity = identity && o.rotation[a * 3 + c] == (a == c ? 1.0 : 0.0);
                 }
-        s.rotated[k] = (any && !identity && o.kind == PHIHIP_OBSTACLE_BOX) ? 1 : 0;
+        s.rotated[k] = (any && !identity && (o.kind == PHIHIP_OBSTACLE_BOX || o.kind == PHIHIP_OBSTACLE_CYLINDER)) ? 1 : 0;
+        if (o.kind == PHIHIP_OBSTACLE_CYLINDER) s.axis[k] = o.reserved + v.ax0;
     }
     return s;
 }
@@ -952,7 +954,20 @@ __device__ __forceinline__ void obstacle_local(const ObstacleSet& s, int k, cons
     }
 }
 
-// lies_inside: box |x - c| <= half (inclusive, phi/geom/_box.py:174-185); sphere |x - c|^2 <= r^2
+// f16, cylinder (phi/geom/_cylinder.py:67-92): h = the frame coordinate along the cylinder's axis, rad2 = the squares of the other two summed in axis
+// order (selected, not indexed: `loc` stays in registers; the skipped term adds an exact 0). `loc`: obstacle_local's frame coordinates, which the box
+// branch shares -- one inlined copy of the rotation per kernel, and the box path stays the fall-through
+__device__ __forceinline__ void cylinder_coords(const ObstacleSet& s, int k, double l0, double l1, double l2, double& rad2, double& h) {
+    const int ax = s.axis[k];
+    const double q0 = ax == 0 ? 0.0 : l0, q1 = ax == 1 ? 0.0 : l1, q2 = ax == 2 ? 0.0 : l2;
+    rad2 = 0;
+    rad2 += q0 * q0;
+    rad2 += q1 * q1;
+    rad2 += q2 * q2;
+    h = ax == 0 ? l0 : (ax == 1 ? l1 : l2);
+}
+
+// lies_inside: box |x - c| <= half (inclusive, phi/geom/_box.py:174-185); sphere |x - c|^2 <= r^2; cylinder rad2 <= R^2 and -depth / 2 <= h <= depth / 2
 __device__ __forceinline__ bool obstacle_inside(const ObstacleSet& s, int k, const double (&x)[3], int ax0) {
     if (s.kind[k] == PHIHIP_OBSTACLE_SPHERE) {
         double d2 = 0;
@@ -962,6 +977,11 @@ __device__ __forceinline__ bool obstacle_inside(const ObstacleSet& s, int k, con
     }
     double loc[3];
     obstacle_local(s, k, x, ax0, loc);
+    if (s.kind[k] == PHIHIP_OBSTACLE_CYLINDER) {
+        double rad2, h;
+        cylinder_coords(s, k, loc[0], loc[1], loc[2], rad2, h);
+        return rad2 <= s.half[k][0] * s.half[k][0] && h >= -s.half[k][1] && h <= s.half[k][1];
+    }
     bool in = true;
     for (int a = ax0; a < 3; ++a) in = in && (((s.skip[k] >> a) & 1) || fabs(loc[a]) <= s.half[k][a]);
     return in;
@@ -977,6 +997,12 @@ __device__ __forceinline__ double obstacle_sdf(const ObstacleSet& s, int k, cons
     }
     double loc[3];
     obstacle_local(s, k, x, ax0, loc);
+    if (s.kind[k] == PHIHIP_OBSTACLE_CYLINDER) {      // max(|r| - R, |h| - depth / 2)
+        double rad2, h;
+        cylinder_coords(s, k, loc[0], loc[1], loc[2], rad2, h);
+        const double mantle = sqrt(rad2) - s.half[k][0], cap = fabs(h) - s.half[k][1];
+        return mantle > cap ? mantle : cap;
+    }
     double dist = -1e300;
     for (int a = ax0; a < 3; ++a) {
         if ((s.skip[k] >> a) & 1) continue;
@@ -992,17 +1018,28 @@ __device__ __forceinline__ double obstacle_sdf(const ObstacleSet& s, int k, cons
 // `margin`: the distance obstacles_near will grow the boxes by. The signed distance of a box is the L-infinity one (obstacle_sdf), so the samples within
 // `margin` of a ROTATED box fill the box grown by `margin` along each of its own axes: its corners lie |half + margin| from the centre, farther than
 // |half| + margin -- the bounding radius stored here is |half + margin| - margin, so that the later `+ margin` reaches them (lies_inside: margin 0).
+// f16: the samples within `margin` of a CYLINDER have |h| <= depth / 2 + margin and |r| <= R + margin in its frame, so along world axis a they lie within
+// cylinder_extent of the centre (up = M e_axis; the rows of M are unit vectors: the radial part of row a has length sqrt(1 - up_a^2)); unrotated this is
+// depth / 2 along the axis and R across it. Not the bounding sphere: a long thin rod would make every patch "near".
+__host__ __device__ __forceinline__ double cylinder_extent(const ObstacleSet& s, int k, int a, double margin) {
+    const double up = s.rot[k][a][s.axis[k]];
+    const double across = 1.0 - up * up;
+    return fabs(up) * (s.half[k][1] + margin) + (s.half[k][0] + margin) * sqrt(across > 0.0 ? across : 0.0) - margin;
+}
+
 __device__ __forceinline__ void obstacle_boxes(const ObstacleSet& s, int ax0, double (*box)[6], double margin) {
     const int k = threadIdx.x;
     if (k < s.count) {
+        const bool cyl = s.kind[k] == PHIHIP_OBSTACLE_CYLINDER;
         double rad = 0;
-        if (s.rotated[k]) {
+        if (s.rotated[k] && !cyl) {
             for (int a = ax0; a < 3; ++a) rad += (s.half[k][a] + margin) * (s.half[k][a] + margin);
             rad = sqrt(rad) - margin;
         }
         for (int a = 0; a < 3; ++a) {
             const bool skip = a < ax0 || ((s.skip[k] >> a) & 1);
-            const double h = s.rotated[k] ? rad : (s.kind[k] == PHIHIP_OBSTACLE_SPHERE ? s.half[k][ax0] : s.half[k][a]);
+            const double h = cyl ? cylinder_extent(s, k, a, margin)
+                                 : (s.rotated[k] ? rad : (s.kind[k] == PHIHIP_OBSTACLE_SPHERE ? s.half[k][ax0] : s.half[k][a]));
             box[k][2 * a] = skip ? -1e300 : s.center[k][a] - h;
             box[k][2 * a + 1] = skip ? 1e300 : s.center[k][a] + h;
         }
@@ -1045,7 +1082,9 @@ static void patch_box_slot(const GridView& v, const ObstacleSet& set, int ca, do
         for (int k = 0; k < set.count; ++k) {
             if ((set.skip[k] >> a) & 1) { lo = -1e300; hi = 1e300; break; }
             double h = set.kind[k] == PHIHIP_OBSTACLE_SPHERE ? set.half[k][v.ax0] : set.half[k][a];
-            if (set.rotated[k]) {      // (the box grown by `margin` along its own axes: obstacle_boxes)
+            if (set.kind[k] == PHIHIP_OBSTACLE_CYLINDER) {
+                h = cylinder_extent(set, k, a, margin);
+            } else if (set.rotated[k]) {      // (the box grown by `margin` along its own axes: obstacle_boxes)
                 double r2 = 0;
                 for (int c = v.ax0; c < 3; ++c) r2 += (set.half[k][c] + margin) * (set.half[k][c] + margin);
                 h = sqrt(r2) - margin;

@@ -11,7 +11,7 @@ from . import field
 from .field import CenteredGrid, Field, StaggeredGrid, assert_close, curl, divergence, laplace, mean, resample, spatial_gradient, where
 from .noise import Noise
 from . import geom
-from .geom import Box, Cuboid, SDFGrid, Sphere, embed, infinite_cylinder, sample_sdf, union, vec
+from .geom import Box, Cuboid, Cylinder, SDFGrid, Sphere, cylinder, embed, infinite_cylinder, sample_sdf, union, vec
 from .fluid import Obstacle
 from .solve import ConvergenceException, Diverged, NotConverged, Solve, SolveInfo, copy_with
 from .linear import solve_linear
@@ -23,7 +23,7 @@ __all__ = [
     'BOUNDARY', 'ONE', 'PERIODIC', 'ZERO', 'ZERO_GRADIENT', 'ConstantExtrapolation', 'combine_sides',
     'CenteredGrid', 'Field', 'StaggeredGrid', 'Noise', 'assert_close', 'divergence', 'mean', 'resample', 'spatial_gradient',
     'field', 'laplace', 'curl', 'where',
-    'geom', 'Box', 'Cuboid', 'Sphere', 'SDFGrid', 'sample_sdf', 'embed', 'infinite_cylinder', 'union', 'vec', 'Obstacle',
+    'geom', 'Box', 'Cuboid', 'Sphere', 'Cylinder', 'cylinder', 'SDFGrid', 'sample_sdf', 'embed', 'infinite_cylinder', 'union', 'vec', 'Obstacle',
     'functional_gradient', 'gradient', 'jacobian', 'l2_loss', 'stop_gradient',
     'ConvergenceException', 'Diverged', 'NotConverged', 'Solve', 'SolveInfo', 'copy_with', 'solve_linear',
     'iterate', 'jit_compile',

@@ -14,14 +14,15 @@ import torch
 from . import _capi, autodiff
 from .extrapolation import pressure_extrapolation
 from .field import Field, _check_pressure_padding, _ptrs, same_grid
-from .geom import Box, Geometry, SDFGrid, Sphere
+from .geom import Box, Cylinder, Geometry, SDFGrid, Sphere
 from .geom import Embedded, Union as Union_
 from .solve import Diverged, NotConverged, Solve, SolveInfo
 
 
 class Obstacle:
     """ An obstacle defines boundary conditions inside a geometry; it can have a linear and an angular velocity
-    (phi/physics/fluid.py:21-91). Geometries: `Box` / `Cuboid`, `Sphere`, unions and embeddings of them, and `SDFGrid` (any shape; linear velocity only). """
+    (phi/physics/fluid.py:21-91). Geometries: `Box` / `Cuboid`, `Sphere`, unions and embeddings of them, `Cylinder` (3-D; in unions too), and `SDFGrid`
+    (any shape; linear velocity only). """
 
     def __init__(self, geometry: Geometry, velocity=0, angular_velocity=0):
         self.geometry = geometry
@@ -131,15 +132,18 @@ def _obstacle_array(obstacles: Sequence[Obstacle], velocity: Field, entry: int =
                 kind, half = _capi.OBSTACLE_SPHERE, [geo.radius] * len(order)
             elif isinstance(geo, Box):
                 kind, half = _capi.OBSTACLE_BOX, [geo.half_size[i] for i in order]
+            elif isinstance(geo, Cylinder):   # f16: (radius, depth / 2, 0), the axis as an index in the velocity's dimension order
+                kind, half = _capi.OBSTACLE_CYLINDER, [geo.radius, .5 * geo.depth, 0.0]
             else:
-                raise NotImplementedError(f"HIP backend: obstacle geometry {type(geo).__name__} is not supported (Box / Cuboid / Sphere / union / SDFGrid)")
+                raise NotImplementedError(f"HIP backend: obstacle geometry {type(geo).__name__} is not supported (Box / Cuboid / Sphere / Cylinder / union / SDFGrid)")
             vel_order = [ob.geometry.dims.index(d) for d in velocity.dims]
             ang = ob.angular_velocity if len(order) == 2 else [ob.angular_velocity[i] for i in vel_order]
             rot = None
-            if isinstance(geo, Box) and geo.rot is not None:
+            if isinstance(geo, (Box, Cylinder)) and geo.rot is not None:
                 rot = [[geo.rot[i][j] for j in order] for i in order]
             items.append(dict(kind=kind, center=[geo.center[i] for i in order], half_size=half, velocity=[ob.velocity[i] for i in vel_order],
-                              angular_velocity=ang, rotation=rot, group=group if len(members) > 1 else 0, embed_mask=embed_mask))
+                              angular_velocity=ang, rotation=rot, group=group if len(members) > 1 else 0, embed_mask=embed_mask,
+                              axis=velocity.dims.index(geo.axis) if isinstance(geo, Cylinder) else 0))
     return _capi.make_obstacles(items), len(items)
 
 
@@ -210,7 +214,7 @@ def make_incompressible(velocity: Field,
 
     Args:
         velocity: `StaggeredGrid`.
-        obstacles: `Obstacle` or `Geometry` or tuple/list thereof (Box / Cuboid / Sphere; stationary, moving or rotating; `SDFGrid` for any other shape: stationary or moving).
+        obstacles: `Obstacle` or `Geometry` or tuple/list thereof (Box / Cuboid / Sphere / Cylinder; stationary, moving or rotating; `SDFGrid` for any other shape: stationary or moving).
         solve: `Solve` object specifying tolerances, `x0` (pressure guess) and `max_iterations`.
         active: (Optional) `CenteredGrid` mask for which cells the pressure should be solved. If given, the total
             divergence is never subtracted, even if all values are 1.

@@ -1,6 +1,6 @@
 """
 Geometry subset needed by the grid fluid step: `Box` / `Cuboid` (domain bounds and box obstacles, optionally rotated) and
-`Sphere` (reference: phi/geom/_box.py:46-236, phi/geom/_sphere.py), and `SDFGrid` / `sample_sdf` for every other shape (a grid of signed distances,
+`Sphere` (reference: phi/geom/_box.py:46-236, phi/geom/_sphere.py), `Cylinder` / `cylinder` (finite, rotated: phi/geom/_cylinder.py), and `SDFGrid` / `sample_sdf` for every other shape (a grid of signed distances,
 phi/geom/_sdf_grid.py:13-298; at the end of this file). Obstacles are rasterised by device kernels
 (`phihip_obstacle_accessible`, `phihip_apply_obstacles`); the host-side `lies_inside` / `approximate_signed_distance` below only
 serve field initialisers such as `CenteredGrid(Sphere(...))`.
@@ -189,6 +189,9 @@ def embed(geometry: Geometry, projected_dims) -> Geometry:
     for name in reversed(geometry.dims):
         if name not in axes:
             axes = (name,) + axes
+    if isinstance(geometry.entry(0), Cylinder):
+        raise NotImplementedError("HIP backend: embed(Cylinder) is not supported (a cylinder already has three dimensions); for a cylinder whose caps lie "
+                                  "outside the domain use infinite_cylinder(...)")
     return Embedded(geometry, axes)
 
 
@@ -337,6 +340,175 @@ class Sphere(Geometry):
 
     def __repr__(self):
         return f"Sphere({dict(zip(self.dims, self.center))}, radius={self.radius})"
+
+
+# ---- f16: finite cylinders (phi/geom/_cylinder.py) ----------------------------------------------------------------------------------
+def _g17(x) -> str:
+    return f"{float(x):.17g}"
+
+
+class Cylinder(Geometry):
+    """ `cylinder(x=1, y=2, z=3, radius=1, depth=4, axis='z')` (phi/geom/_cylinder.py:16-154): centre, radius, depth, the dim it is aligned with in
+    its own frame, and an optional (3, 3) matrix `rot` (cylinder frame -> world, rows and columns in the order of `dims`). With
+    local = rot^T (x - center), h = local[axis] and r the other two components:
+        lies_inside(x)                 = r.r <= radius^2 and -depth / 2 <= h <= depth / 2, all inclusive          (:67-72)
+        approximate_signed_distance(x) = max(|r| - radius, |h| - depth / 2)                                       (:74-92)
+    Three dimensions only; as an obstacle it is rasterised by the device kernels (kind PHIHIP_OBSTACLE_CYLINDER), may rotate, move, carry an angular
+    velocity and be a member of a union. Radius, depth or a centre coordinate given as 1-D sequences make a `Batched` geometry. """
+
+    def __new__(cls, center=None, radius=None, depth=None, axis=None, rot=None):
+        if center is not None:
+            n = _batch_len(radius, depth, *dict(center).values())
+            if n:
+                return Batched([Cylinder({d: _pick(c, i) for d, c in dict(center).items()}, _pick(radius, i), _pick(depth, i), axis, rot) for i in range(n)])
+        return super().__new__(cls)
+
+    def __init__(self, center, radius, depth, axis, rot=None):
+        center = dict(center)
+        self.dims = tuple(center.keys())
+        if len(self.dims) != 3:
+            raise NotImplementedError(f"HIP backend: a Cylinder needs three dimensions, got {self.dims}: in 2-D use a Box (radius across, depth along the axis), "
+                                      f"or a Sphere for the disc")
+        assert axis in self.dims, f"Cylinder axis {axis!r} is not one of {self.dims}"
+        self.center = tuple(float(c) for c in center.values())
+        self.radius, self.depth, self.axis = float(radius), float(depth), axis
+        if rot is not None:
+            rot = np.asarray(rot, dtype=float)
+            if rot.shape != (3, 3):
+                raise NotImplementedError(f"HIP backend: a Cylinder rotates by a (3, 3) rotation matrix (got shape {rot.shape}): build the matrix from the "
+                                          f"angles, as for Box.rotated in 3-D")
+        self.rot = rot
+
+    @property
+    def rotation(self):
+        return self.rot
+
+    @property
+    def radial_axes(self):
+        return tuple(d for d in self.dims if d != self.axis)
+
+    @property
+    def volume(self) -> float:
+        return float(np.pi * self.radius ** 2 * self.depth)                  # (:46-47)
+
+    @property
+    def up(self):
+        """ the axis in world coordinates: rot e_axis (:50-51) """
+        e = np.zeros(3)
+        e[self.dims.index(self.axis)] = 1.0
+        return e if self.rot is None else self.rot @ e
+
+    def _rh(self, points):
+        """ (r.r, h) of `points` (one array per dim) in the cylinder's frame: rot^T (x - center), the two radial squares summed in dim order """
+        r = [np.asarray(points[a], np.float64) - self.center[a] for a in range(3)]
+        if self.rot is not None:
+            r = [sum(self.rot[c][a] * r[c] for c in range(3)) for a in range(3)]
+        ax = self.dims.index(self.axis)
+        rad = [r[a] for a in range(3) if a != ax]
+        return rad[0] * rad[0] + rad[1] * rad[1], r[ax]
+
+    def lies_inside(self, points):
+        rad2, h = self._rh(points)
+        return (rad2 <= self.radius ** 2) & (h >= -.5 * self.depth) & (h <= .5 * self.depth)
+
+    def approximate_signed_distance(self, points):
+        rad2, h = self._rh(points)
+        return np.maximum(np.sqrt(rad2) - self.radius, np.abs(h) - .5 * self.depth)
+
+    def bounding_radius(self) -> float:
+        return float(np.sqrt(self.radius ** 2 + (.5 * self.depth) ** 2))     # (:137-138)
+
+    def bounding_half_extent(self, epsilon=1e-5):
+        """ (:140-144), the epsilon under the root included; in the order of `dims` """
+        if self.rot is not None:
+            up = self.up
+            return tuple(float(x) for x in np.abs(up) * .5 * self.depth + self.radius * np.sqrt(np.maximum(epsilon, 1 - up ** 2)))
+        return tuple(.5 * self.depth if d == self.axis else self.radius for d in self.dims)
+
+    def _with(self, **kw):
+        args = dict(center=dict(zip(self.dims, self.center)), radius=self.radius, depth=self.depth, axis=self.axis, rot=self.rot)
+        args.update(kw)
+        return Cylinder(**args)
+
+    def at(self, center):
+        center = [center.get(d, c) for d, c in zip(self.dims, self.center)] if isinstance(center, dict) else list(center)
+        return self._with(center=dict(zip(self.dims, center)))
+
+    def shifted(self, delta):
+        delta = [delta.get(d, 0.0) for d in self.dims] if isinstance(delta, dict) else list(delta)
+        return self._with(center={d: c + dd for d, c, dd in zip(self.dims, self.center, delta)})
+
+    def rotated(self, angle):
+        """ rotation = rotation @ Q (:149-151); Q: a (3, 3) rotation matrix """
+        Q = np.asarray(angle, dtype=float)
+        if Q.shape != (3, 3):
+            raise NotImplementedError(f"HIP backend: Cylinder.rotated takes a (3, 3) rotation matrix (got shape {Q.shape}): build the matrix from the angles, "
+                                      f"as for Box.rotated in 3-D")
+        return self._with(rot=Q if self.rot is None else self.rot @ Q)
+
+    def scaled(self, factor):
+        return self._with(radius=self.radius * float(factor), depth=self.depth * float(factor))      # (:153-154)
+
+    def with_radius(self, radius):
+        return self._with(radius=radius)
+
+    def with_depth(self, depth):
+        return self._with(depth=depth)
+
+    def __repr__(self):
+        # (fluid._MaskCache keys on this: every parameter with 17 significant digits, the rotation included)
+        rot = "" if self.rot is None else ", rot=[" + ",".join(_g17(x) for x in self.rot.reshape(-1)) + "]"
+        return ("Cylinder(" + ", ".join(f"{d}={_g17(c)}" for d, c in zip(self.dims, self.center)) +
+                f", radius={_g17(self.radius)}, depth={_g17(self.depth)}, axis={self.axis!r}{rot})")
+
+
+def _rotation_onto(direction: np.ndarray) -> np.ndarray:
+    """ a rotation matrix that takes e_last = (0, 0, 1) to direction / |direction|, by Rodrigues' formula R = I + [v]x + [v]x^2 / (1 + c) with
+    v = e x d, c = e . d. The formula has a pole at c = -1 (antiparallel) and loses digits near it: a direction in the lower half space is reached by the
+    half turn about the first axis (e -> -e) followed by the rotation from -e, for which 1 + c >= 1 """
+    d = np.asarray(direction, dtype=float)
+    norm = float(np.sqrt((d * d).sum()))
+    assert norm > 0, "the cylinder's axis vector must not be zero"
+    d = d / norm
+
+    def rodrigues(e):
+        v, c = np.cross(e, d), float(e @ d)
+        K = np.array([[0.0, -v[2], v[1]], [v[2], 0.0, -v[0]], [-v[1], v[0], 0.0]])
+        return np.eye(3) + K + (K @ K) / (1.0 + c)
+    e = np.array([0.0, 0.0, 1.0])
+    if float(e @ d) >= 0:
+        return rodrigues(e)
+    return rodrigues(-e) @ np.diag([1.0, -1.0, -1.0])
+
+
+def cylinder(center=None, radius=None, depth=None, rotation=None, axis=-1, **center_) -> Geometry:
+    """ `cylinder(x=1, y=2, z=3, radius=1, depth=4, axis='x')` / `cylinder(vec(x=1, y=2, z=3), radius=1, depth=4, rotation=M)` (phi/geom/_cylinder.py:206-257).
+    axis: an int or a dim name -- the dim the cylinder is aligned with before `rotation` (None or a (3, 3) matrix) turns it; or a direction `vec(x=.., y=.., z=..)`:
+    then `rotation` must be None, the stored axis is the last dim and depth defaults to 2 |axis|. [PHIML-RECALL] the reference builds that matrix with
+    PhiML's rotation_matrix_from_directions; here Rodrigues' formula (`_rotation_onto`). Any rotation taking e_last to the direction describes the same body:
+    only the stored matrix can differ from the reference's, no sampled value. """
+    if center is not None:
+        if not isinstance(center, dict):
+            assert center == 0 and isinstance(axis, dict), "center must be a vec(...) (or 0 with a vector-valued axis)"
+            center = {d: 0.0 for d in axis}
+        center = dict(center)
+    else:
+        center = dict(center_)
+    assert radius is not None, "radius must be specified"
+    dims = tuple(center.keys())
+    if isinstance(axis, dict):      # the cylinder's axis as a direction vector
+        assert rotation is None, "when the axis is given as a vector, rotation must be None"
+        assert set(axis) == set(dims), f"the axis vector {tuple(axis)} must have the dims of the center {dims}"
+        direction = np.array([float(axis[d]) for d in dims])
+        if depth is None:
+            depth = 2.0 * float(np.sqrt((direction * direction).sum()))
+        if len(dims) == 3:
+            rotation = _rotation_onto(direction)
+        axis = dims[-1]
+    else:
+        assert depth is not None, "depth must be specified (or the axis given as a vector)"
+        axis = dims[axis] if isinstance(axis, (int, np.integer)) else axis
+    return Cylinder(center, radius, depth, axis, rotation)
 
 
 # ---- f13: arbitrary shapes from a signed-distance grid (phi/geom/_sdf_grid.py) ------------------------------------------------------
@@ -553,9 +725,9 @@ def _bounding_box(geometry: Geometry) -> Box:
     if isinstance(geometry, Box):
         half = geometry.half_size if geometry.rot is None else tuple(np.abs(geometry.rot) @ np.asarray(geometry.half_size))      # _box.py:168-172
         return Box(**{d: (c - h, c + h) for d, c, h in zip(geometry.dims, geometry.center, half)})
-    if isinstance(geometry, SDFGrid):
+    if isinstance(geometry, (SDFGrid, Cylinder)):
         return Box(**{d: (c - h, c + h) for d, c, h in zip(geometry.dims, geometry.center, geometry.bounding_half_extent())})
-    raise NotImplementedError(f"HIP backend: sample_sdf of {type(geometry).__name__} is not supported (Box / Cuboid / Sphere / union)")
+    raise NotImplementedError(f"HIP backend: sample_sdf of {type(geometry).__name__} is not supported (Box / Cuboid / Sphere / Cylinder / union)")
 
 
 def sample_sdf(geometry: Geometry, bounds: Box = None, resolution: Dict[str, int] = None, approximate_outside=False, rebuild=None, valid_dist=None,
@@ -563,7 +735,7 @@ def sample_sdf(geometry: Geometry, bounds: Box = None, resolution: Dict[str, int
     """ `sample_sdf(geometry, bounds, x=64, y=32)` (phi/geom/_sdf_grid.py:245-298): an SDFGrid of `geometry.approximate_signed_distance` at the
     centres of the cells of `bounds`; center, volume and bounding_radius come from the geometry (a union: the centre of its bounding box, the
     other two from the grid). Default bounds: the geometry's bounding box with half_size * (1 + 2 rel_margin) + 2 abs_margin (:273-274).
-    `approximate_outside` defaults to False here and to True in `SDFGrid(...)`, as in the reference. Box / Cuboid (rotated too), Sphere and
+    `approximate_outside` defaults to False here and to True in `SDFGrid(...)`, as in the reference. Box / Cuboid (rotated too), Sphere, Cylinder and
     unions of them are evaluated on the device (`phihip_sdf_from_analytic`); `dtype`: element type of the array. """
     if rebuild is not None or cache_surface or valid_dist is not None:
         what = "rebuild" if rebuild is not None else ("cache_surface" if cache_surface else "valid_dist")
@@ -587,8 +759,11 @@ def sample_sdf(geometry: Geometry, bounds: Box = None, resolution: Dict[str, int
         elif isinstance(g, Box):
             rot = None if g.rot is None else [[g.rot[i][j] for j in order] for i in order]
             items.append(dict(kind=0, center=[g.center[i] for i in order], half_size=[g.half_size[i] for i in order], rotation=rot))
+        elif isinstance(g, Cylinder):
+            rot = None if g.rot is None else [[g.rot[i][j] for j in order] for i in order]
+            items.append(dict(kind=3, center=[g.center[i] for i in order], half_size=[g.radius, .5 * g.depth, 0.0], rotation=rot, axis=dims.index(g.axis)))
         else:
-            raise NotImplementedError(f"HIP backend: sample_sdf of {type(g).__name__} is not supported (Box / Cuboid / Sphere / union)")
+            raise NotImplementedError(f"HIP backend: sample_sdf of {type(g).__name__} is not supported (Box / Cuboid / Sphere / Cylinder / union)")
     import torch
     from . import _capi
     from .backend import default_backend
@@ -604,6 +779,9 @@ def sample_sdf(geometry: Geometry, bounds: Box = None, resolution: Dict[str, int
         D = len(dims)
         volume = {2: np.pi * geometry.radius ** 2, 3: 4 / 3 * np.pi * geometry.radius ** 3}.get(D, 2 * geometry.radius)
         center, radius = [geometry.center[geometry.dims.index(d)] for d in dims], geometry.radius
+    elif isinstance(geometry, Cylinder):
+        volume, radius = geometry.volume, geometry.bounding_radius()
+        center = [geometry.center[geometry.dims.index(d)] for d in dims]
     else:
         volume = float(np.prod(geometry.size))
         center, radius = [geometry.center[geometry.dims.index(d)] for d in dims], float(np.sqrt(sum(h * h for h in geometry.half_size)))      # _box.py:209-210
