@@ -721,13 +721,9 @@ int run_advect_staggered_bwd(phihip_ctx* ctx, const GridView& v, const void* con
                              void* const gf[3], void* const gv[3], double dt, hipStream_t s) {
     const VelGrid g = make_velgrid(v);
     LaunchScope ls(ctx, PHIHIP_K_ADVECT, s);
-    if (v.dtype == PHIHIP_F64) {
-        if (v.rank == 3) PHIHIP_TRY((advect_staggered_bwd_t<double, 3>(ctx, v, g, f, vel, gout, gf, gv, dt, s)));
-        else PHIHIP_TRY((advect_staggered_bwd_t<double, 2>(ctx, v, g, f, vel, gout, gf, gv, dt, s)));
-    } else {
-        if (v.rank == 3) PHIHIP_TRY((advect_staggered_bwd_t<float, 3>(ctx, v, g, f, vel, gout, gf, gv, dt, s)));
-        else PHIHIP_TRY((advect_staggered_bwd_t<float, 2>(ctx, v, g, f, vel, gout, gf, gv, dt, s)));
-    }
+    PHIHIP_TRY(with_dtype_rank(v, [&](auto t, auto d) {
+        return advect_staggered_bwd_t<typename decltype(t)::type, decltype(d)::value>(ctx, v, g, f, vel, gout, gf, gv, dt, s);
+    }));
     PHIHIP_CHECK_HIP(hipGetLastError());
     return PHIHIP_OK;
 }
@@ -751,13 +747,9 @@ int run_advect_centered_bwd(phihip_ctx* ctx, const GridView& v, const void* sfie
     const VelGrid g = make_velgrid(v);
     const ScalarBc sb = make_scalar_bc(v, s_bc, s_val);
     LaunchScope ls(ctx, PHIHIP_K_ADVECT, s);
-    if (v.dtype == PHIHIP_F64) {
-        if (v.rank == 3) PHIHIP_TRY((advect_centered_bwd_t<double, 3>(ctx, v, g, sb, sfield, vel, gout, gs, gv, dt, s)));
-        else PHIHIP_TRY((advect_centered_bwd_t<double, 2>(ctx, v, g, sb, sfield, vel, gout, gs, gv, dt, s)));
-    } else {
-        if (v.rank == 3) PHIHIP_TRY((advect_centered_bwd_t<float, 3>(ctx, v, g, sb, sfield, vel, gout, gs, gv, dt, s)));
-        else PHIHIP_TRY((advect_centered_bwd_t<float, 2>(ctx, v, g, sb, sfield, vel, gout, gs, gv, dt, s)));
-    }
+    PHIHIP_TRY(with_dtype_rank(v, [&](auto t, auto d) {
+        return advect_centered_bwd_t<typename decltype(t)::type, decltype(d)::value>(ctx, v, g, sb, sfield, vel, gout, gs, gv, dt, s);
+    }));
     PHIHIP_CHECK_HIP(hipGetLastError());
     return PHIHIP_OK;
 }
@@ -768,12 +760,11 @@ int run_centered_to_staggered_bwd(phihip_ctx* ctx, const GridView& v, const int3
     const ScalarBc sb = make_scalar_bc(v, s_bc, nullptr);
     LaunchScope ls(ctx, PHIHIP_K_OTHER, s);
     const dim3 grid(bwd_blocks(v.cells), v.batch);
-    if (v.dtype == PHIHIP_F64)
-        hipLaunchKernelGGL(c2s_bwd_kernel<double>, grid, dim3(kBlock), 0, s, g, sb, (CComp3a<double>{{(const double*)gout[0], (const double*)gout[1], (const double*)gout[2]}}),
-                           (double*)gs, vector[0], vector[1], vector[2]);
-    else
-        hipLaunchKernelGGL(c2s_bwd_kernel<float>, grid, dim3(kBlock), 0, s, g, sb, (CComp3a<float>{{(const float*)gout[0], (const float*)gout[1], (const float*)gout[2]}}),
-                           (float*)gs, (float)vector[0], (float)vector[1], (float)vector[2]);
+    with_dtype(v, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(c2s_bwd_kernel<T>, grid, dim3(kBlock), 0, s, g, sb, (CComp3a<T>{{(const T*)gout[0], (const T*)gout[1], (const T*)gout[2]}}), (T*)gs,
+                           (T)vector[0], (T)vector[1], (T)vector[2]);
+    });
     PHIHIP_CHECK_HIP(hipGetLastError());
     return PHIHIP_OK;
 }
@@ -826,7 +817,7 @@ static int launch_mc_staggered_bwd(phihip_ctx* ctx, const GridView& v, const Vel
 
 // scratch layout for the MacCormack adjoints: [fwd | g_fwd] per component, 256-byte aligned
 static int mc_scratch(phihip_ctx* ctx, const GridView& v, bool staggered, void* fwd[3], void* gfwd[3]) {
-    const size_t esize = v.dtype == PHIHIP_F64 ? 8 : 4;
+    const size_t esize = elem_bytes(v);
     size_t offs[3] = {0, 0, 0}, total = 0;
     for (int ca = staggered ? v.ax0 : 2; ca < 3; ++ca) {
         offs[ca] = total;
@@ -847,17 +838,13 @@ int run_mac_cormack_staggered_bwd(phihip_ctx* ctx, const GridView& v, const void
     void *fwd[3], *gfwd[3];
     PHIHIP_TRY(mc_scratch(ctx, v, true, fwd, gfwd));
     PHIHIP_TRY(run_advect_staggered(ctx, v, f, vel, fwd, dt, s));                                // recompute the forward intermediate
-    const size_t esize = v.dtype == PHIHIP_F64 ? 8 : 4;
+    const size_t esize = elem_bytes(v);
     for (int ca = v.ax0; ca < 3; ++ca) PHIHIP_CHECK_HIP(hipMemsetAsync(gfwd[ca], 0, (size_t)v.batch * v.ccells[ca] * esize, s));
     {
         LaunchScope ls(ctx, PHIHIP_K_ADVECT, s);
-        if (v.dtype == PHIHIP_F64) {
-            if (v.rank == 3) PHIHIP_TRY((launch_mc_staggered_bwd<double, 3>(ctx, v, g, f, vel, fwd, gout, gfwd, gf, gv, dt, 0.5 * strength, s)));
-            else PHIHIP_TRY((launch_mc_staggered_bwd<double, 2>(ctx, v, g, f, vel, fwd, gout, gfwd, gf, gv, dt, 0.5 * strength, s)));
-        } else {
-            if (v.rank == 3) PHIHIP_TRY((launch_mc_staggered_bwd<float, 3>(ctx, v, g, f, vel, fwd, gout, gfwd, gf, gv, dt, 0.5 * strength, s)));
-            else PHIHIP_TRY((launch_mc_staggered_bwd<float, 2>(ctx, v, g, f, vel, fwd, gout, gfwd, gf, gv, dt, 0.5 * strength, s)));
-        }
+        PHIHIP_TRY(with_dtype_rank(v, [&](auto t, auto d) {
+            return launch_mc_staggered_bwd<typename decltype(t)::type, decltype(d)::value>(ctx, v, g, f, vel, fwd, gout, gfwd, gf, gv, dt, 0.5 * strength, s);
+        }));
     }
     const void* cg[3] = {gfwd[0], gfwd[1], gfwd[2]};
     PHIHIP_TRY(run_advect_staggered_bwd(ctx, v, f, vel, cg, gf, gv, dt, s));                     // g_fwd -> field, velocity
@@ -889,17 +876,13 @@ int run_mac_cormack_centered_bwd(phihip_ctx* ctx, const GridView& v, const void*
     void *fwd[3], *gfwd[3];
     PHIHIP_TRY(mc_scratch(ctx, v, false, fwd, gfwd));
     PHIHIP_TRY(run_advect_centered(ctx, v, sfield, s_bc, s_val, vel, fwd[2], dt, s));
-    const size_t esize = v.dtype == PHIHIP_F64 ? 8 : 4;
+    const size_t esize = elem_bytes(v);
     PHIHIP_CHECK_HIP(hipMemsetAsync(gfwd[2], 0, (size_t)v.batch * v.cells * esize, s));
     {
         LaunchScope ls(ctx, PHIHIP_K_ADVECT, s);
-        if (v.dtype == PHIHIP_F64) {
-            if (v.rank == 3) PHIHIP_TRY((launch_mc_centered_bwd<double, 3>(ctx, v, g, sb, sfield, vel, fwd[2], gout, gfwd[2], gs, gv, dt, 0.5 * strength, s)));
-            else PHIHIP_TRY((launch_mc_centered_bwd<double, 2>(ctx, v, g, sb, sfield, vel, fwd[2], gout, gfwd[2], gs, gv, dt, 0.5 * strength, s)));
-        } else {
-            if (v.rank == 3) PHIHIP_TRY((launch_mc_centered_bwd<float, 3>(ctx, v, g, sb, sfield, vel, fwd[2], gout, gfwd[2], gs, gv, dt, 0.5 * strength, s)));
-            else PHIHIP_TRY((launch_mc_centered_bwd<float, 2>(ctx, v, g, sb, sfield, vel, fwd[2], gout, gfwd[2], gs, gv, dt, 0.5 * strength, s)));
-        }
+        PHIHIP_TRY(with_dtype_rank(v, [&](auto t, auto d) {
+            return launch_mc_centered_bwd<typename decltype(t)::type, decltype(d)::value>(ctx, v, g, sb, sfield, vel, fwd[2], gout, gfwd[2], gs, gv, dt, 0.5 * strength, s);
+        }));
     }
     PHIHIP_TRY(run_advect_centered_bwd(ctx, v, sfield, s_bc, s_val, vel, gfwd[2], gs, gv, dt, s));
     PHIHIP_CHECK_HIP(hipGetLastError());
@@ -1004,8 +987,7 @@ static int project_bwd_t(phihip_ctx* ctx, const GridView& v0, const uint8_t* fla
 
 int run_project_bwd(phihip_ctx* ctx, const GridView& v, const uint8_t* flags, int mask_batch, int balance, void* const gv[3], const void* gp,
                     const phihip_solve* solve, phihip_solve_info* info, hipStream_t s) {
-    return v.dtype == PHIHIP_F64 ? project_bwd_t<double>(ctx, v, flags, mask_batch, balance, gv, gp, solve, info, s)
-                                 : project_bwd_t<float>(ctx, v, flags, mask_batch, balance, gv, gp, solve, info, s);
+    return with_dtype(v, [&](auto t) { return project_bwd_t<typename decltype(t)::type>(ctx, v, flags, mask_batch, balance, gv, gp, solve, info, s); });
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1049,15 +1031,13 @@ int run_grid_sample_bwd(phihip_ctx* ctx, const GridView& v, const int32_t s_bc[3
     const long long vstride = values_batch > 1 ? v.cells : 0;   // shared values: every batch entry scatters into the same gradient
     const unsigned nblk = (unsigned)((npts + kBlock - 1) / kBlock < 65536 ? (npts + kBlock - 1) / kBlock : 65536);
     LaunchScope ls(ctx, PHIHIP_K_ADVECT, s);
-    if (npts > 0) {
-#define PHIHIP_GSB(T, DIM)                                                                                                                           \
-    hipLaunchKernelGGL((grid_sample_bwd_kernel<T, DIM>), dim3(nblk, v.batch), dim3(kBlock), 0, s, sb, v.n[0], v.n[1], v.n[2], (const T*)values, vstride, \
-                       (CComp3a<T>{{(const T*)coords[0], (const T*)coords[1], (const T*)coords[2]}}), npts, (const T*)gout, (T*)gvalues,               \
-                       (Comp3w<T>{{gcoords ? (T*)gcoords[0] : nullptr, gcoords ? (T*)gcoords[1] : nullptr, gcoords ? (T*)gcoords[2] : nullptr}}))
-        if (v.dtype == PHIHIP_F64) { if (v.rank == 3) PHIHIP_GSB(double, 3); else PHIHIP_GSB(double, 2); }
-        else { if (v.rank == 3) PHIHIP_GSB(float, 3); else PHIHIP_GSB(float, 2); }
-#undef PHIHIP_GSB
-    }
+    if (npts > 0)
+        with_dtype_rank(v, [&](auto t, auto d) {
+            using T = typename decltype(t)::type;
+            hipLaunchKernelGGL((grid_sample_bwd_kernel<T, decltype(d)::value>), dim3(nblk, v.batch), dim3(kBlock), 0, s, sb, v.n[0], v.n[1], v.n[2], (const T*)values,
+                               vstride, (CComp3a<T>{{(const T*)coords[0], (const T*)coords[1], (const T*)coords[2]}}), npts, (const T*)gout, (T*)gvalues,
+                               (Comp3w<T>{{gcoords ? (T*)gcoords[0] : nullptr, gcoords ? (T*)gcoords[1] : nullptr, gcoords ? (T*)gcoords[2] : nullptr}}));
+        });
     PHIHIP_CHECK_HIP(hipGetLastError());
     return PHIHIP_OK;
 }

@@ -137,13 +137,7 @@ static void launch_advect_staggered(const GridView& v, const VelGrid& g, const v
 template <int MODE>
 static void dispatch_advect_staggered(const GridView& v, const VelGrid& g, const void* const f[3], const void* const vel[3],
                                       const void* const fwd[3], void* const out[3], double dt, double ch, hipStream_t s) {
-    if (v.dtype == PHIHIP_F64) {
-        if (v.rank == 3) launch_advect_staggered<double, 3, MODE>(v, g, f, vel, fwd, out, dt, ch, s);
-        else launch_advect_staggered<double, 2, MODE>(v, g, f, vel, fwd, out, dt, ch, s);
-    } else {
-        if (v.rank == 3) launch_advect_staggered<float, 3, MODE>(v, g, f, vel, fwd, out, dt, ch, s);
-        else launch_advect_staggered<float, 2, MODE>(v, g, f, vel, fwd, out, dt, ch, s);
-    }
+    with_dtype_rank(v, [&](auto t, auto d) { launch_advect_staggered<typename decltype(t)::type, decltype(d)::value, MODE>(v, g, f, vel, fwd, out, dt, ch, s); });
 }
 
 static int check_advect_sizes(const GridView& v) {
@@ -197,7 +191,7 @@ int run_mac_cormack_staggered(phihip_ctx* ctx, const GridView& v, const void* co
                               double dt, double strength, hipStream_t s) {
     PHIHIP_TRY(check_advect_sizes(v));
     const VelGrid g = make_velgrid(v);
-    const size_t esize = v.dtype == PHIHIP_F64 ? 8 : 4;
+    const size_t esize = elem_bytes(v);
     size_t offs[3] = {0, 0, 0}, total = 0;
     for (int ca = v.ax0; ca < 3; ++ca) {
         offs[ca] = total;
@@ -249,13 +243,7 @@ static void launch_advect_centered(const GridView& v, const VelGrid& g, const Sc
 template <int MODE>
 static void dispatch_advect_centered(const GridView& v, const VelGrid& g, const ScalarBc& sb, const void* sfield, const void* const vel[3],
                                      const void* fwd, void* out, double dt, double ch, hipStream_t s) {
-    if (v.dtype == PHIHIP_F64) {
-        if (v.rank == 3) launch_advect_centered<double, 3, MODE>(v, g, sb, sfield, vel, fwd, out, dt, ch, s);
-        else launch_advect_centered<double, 2, MODE>(v, g, sb, sfield, vel, fwd, out, dt, ch, s);
-    } else {
-        if (v.rank == 3) launch_advect_centered<float, 3, MODE>(v, g, sb, sfield, vel, fwd, out, dt, ch, s);
-        else launch_advect_centered<float, 2, MODE>(v, g, sb, sfield, vel, fwd, out, dt, ch, s);
-    }
+    with_dtype_rank(v, [&](auto t, auto d) { launch_advect_centered<typename decltype(t)::type, decltype(d)::value, MODE>(v, g, sb, sfield, vel, fwd, out, dt, ch, s); });
 }
 
 int run_advect_centered(phihip_ctx* ctx, const GridView& v, const void* sfield, const int32_t s_bc[3][2], const double s_val[3][2],
@@ -283,7 +271,7 @@ int run_mac_cormack_centered(phihip_ctx* ctx, const GridView& v, const void* sfi
     PHIHIP_TRY(check_advect_sizes(v));
     const VelGrid g = make_velgrid(v);
     const ScalarBc sb = make_scalar_bc(v, s_bc, s_val);
-    const size_t esize = v.dtype == PHIHIP_F64 ? 8 : 4;
+    const size_t esize = elem_bytes(v);
     PHIHIP_TRY(ensure_buffer(ctx->ws_adv, (size_t)v.batch * v.cells * esize));
     // both passes from LDS windows (advect_win.hip), each with the reach its own history asks for; a pass that keeps the gather kernel reads /
     // writes the same buffers
@@ -357,14 +345,12 @@ int run_grid_sample(phihip_ctx* ctx, const GridView& v, const int32_t s_bc[3][2]
     const long long vstride = values_batch > 1 ? v.cells : 0;
     const unsigned nblk = (unsigned)((npts + kBlock - 1) / kBlock < 65536 ? (npts + kBlock - 1) / kBlock : 65536);
     LaunchScope ls(ctx, PHIHIP_K_ADVECT, s);
-    if (npts > 0) {
-#define PHIHIP_GS(T, DIM)                                                                                                                       \
-    hipLaunchKernelGGL((grid_sample_kernel<T, DIM>), dim3(nblk, v.batch), dim3(kBlock), 0, s, sb, v.n[0], v.n[1], v.n[2], (const T*)values, vstride, \
-                       (CComp3a<T>{{(const T*)coords[0], (const T*)coords[1], (const T*)coords[2]}}), npts, (T*)out, (T*)out_min, (T*)out_max)
-        if (v.dtype == PHIHIP_F64) { if (v.rank == 3) PHIHIP_GS(double, 3); else PHIHIP_GS(double, 2); }
-        else { if (v.rank == 3) PHIHIP_GS(float, 3); else PHIHIP_GS(float, 2); }
-#undef PHIHIP_GS
-    }
+    if (npts > 0)
+        with_dtype_rank(v, [&](auto t, auto d) {
+            using T = typename decltype(t)::type;
+            hipLaunchKernelGGL((grid_sample_kernel<T, decltype(d)::value>), dim3(nblk, v.batch), dim3(kBlock), 0, s, sb, v.n[0], v.n[1], v.n[2], (const T*)values,
+                               vstride, (CComp3a<T>{{(const T*)coords[0], (const T*)coords[1], (const T*)coords[2]}}), npts, (T*)out, (T*)out_min, (T*)out_max);
+        });
     PHIHIP_CHECK_HIP(hipGetLastError());
     return PHIHIP_OK;
 }

@@ -14,6 +14,7 @@
 //                            _resample.py:148-153): component d at a d-face = mean of component d in the two adjacent cells, outside cells
 //                            from the centred field's extrapolation.
 // All three are gather kernels, one launch each for every component and batch entry; index math is 32-bit inside one batch entry.
+// The run_* functions pick <T, DIM> with with_dtype_rank / with_dtype (common.hpp); the component count NC is chosen inside that lambda.
 #pragma once
 
 namespace phihip {
@@ -117,19 +118,14 @@ int run_advect_cvec(phihip_ctx* ctx, const GridView& v, const void* field, int f
     const long long fstride = field_batch > 1 ? (long long)C * v.cells : 0, vstride = vel_batch > 1 ? (long long)v.rank * v.cells : 0;
     LaunchScope ls(ctx, PHIHIP_K_ADVECT, s);
     const dim3 grid((unsigned)sample_blocks(v.n), v.batch);
-#define PHIHIP_CV_NC(T, DIM, NC)                                                                                                            \
-    hipLaunchKernelGGL((advect_cvec_kernel<T, DIM, NC>), grid, dim3(kBlock), 0, s, g, sb, (const T*)field, fstride, C, (const T*)vel, vstride, \
-                       (T*)out, (T)dt)
-#define PHIHIP_CV(T, DIM)                                                                    \
-    do {                                                                                     \
-        if (C == 1) PHIHIP_CV_NC(T, DIM, 1);                                                 \
-        else if (C == DIM) PHIHIP_CV_NC(T, DIM, DIM);                                        \
-        else PHIHIP_CV_NC(T, DIM, 0);                                                        \
-    } while (0)
-    if (v.dtype == PHIHIP_F64) { if (v.rank == 3) PHIHIP_CV(double, 3); else PHIHIP_CV(double, 2); }
-    else { if (v.rank == 3) PHIHIP_CV(float, 3); else PHIHIP_CV(float, 2); }
-#undef PHIHIP_CV
-#undef PHIHIP_CV_NC
+    with_dtype_rank(v, [&](auto t, auto d) {
+        using T = typename decltype(t)::type;
+        constexpr int DIM = decltype(d)::value;
+        const T *f = (const T*)field, *u = (const T*)vel;
+        if (C == 1) hipLaunchKernelGGL((advect_cvec_kernel<T, DIM, 1>), grid, dim3(kBlock), 0, s, g, sb, f, fstride, C, u, vstride, (T*)out, (T)dt);
+        else if (C == DIM) hipLaunchKernelGGL((advect_cvec_kernel<T, DIM, DIM>), grid, dim3(kBlock), 0, s, g, sb, f, fstride, C, u, vstride, (T*)out, (T)dt);
+        else hipLaunchKernelGGL((advect_cvec_kernel<T, DIM, 0>), grid, dim3(kBlock), 0, s, g, sb, f, fstride, C, u, vstride, (T*)out, (T)dt);
+    });
     PHIHIP_CHECK_HIP(hipGetLastError());
     return PHIHIP_OK;
 }
@@ -140,12 +136,11 @@ int run_staggered_to_cvec(phihip_ctx* ctx, const GridView& v, const void* const 
     const VelGrid g = make_velgrid(v);
     LaunchScope ls(ctx, PHIHIP_K_ADVECT, s);
     const dim3 grid((unsigned)sample_blocks(v.n), v.batch);
-#define PHIHIP_SC(T, DIM)                                                                                                                   \
-    hipLaunchKernelGGL((staggered_to_cvec_kernel<T, DIM>), grid, dim3(kBlock), 0, s, g, (CComp3a<T>{{(const T*)vel[0], (const T*)vel[1], (const T*)vel[2]}}), \
-                       (T*)out)
-    if (v.dtype == PHIHIP_F64) { if (v.rank == 3) PHIHIP_SC(double, 3); else PHIHIP_SC(double, 2); }
-    else { if (v.rank == 3) PHIHIP_SC(float, 3); else PHIHIP_SC(float, 2); }
-#undef PHIHIP_SC
+    with_dtype_rank(v, [&](auto t, auto d) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((staggered_to_cvec_kernel<T, decltype(d)::value>), grid, dim3(kBlock), 0, s, g,
+                           (CComp3a<T>{{(const T*)vel[0], (const T*)vel[1], (const T*)vel[2]}}), (T*)out);
+    });
     PHIHIP_CHECK_HIP(hipGetLastError());
     return PHIHIP_OK;
 }
@@ -162,12 +157,10 @@ int run_cvec_to_faces(phihip_ctx* ctx, const GridView& v, const void* field, int
     const int nblk = ceil_div(most, kBlock) < 16384 ? ceil_div(most, kBlock) : 16384;
     LaunchScope ls(ctx, PHIHIP_K_ADVECT, s);
     const dim3 grid((unsigned)nblk, v.batch, v.rank);
-    if (v.dtype == PHIHIP_F64)
-        hipLaunchKernelGGL(cvec_to_faces_kernel<double>, grid, dim3(kBlock), 0, s, g, sb, (const double*)field, fstride,
-                           (WComp3<double>{{(double*)out[0], (double*)out[1], (double*)out[2]}}));
-    else
-        hipLaunchKernelGGL(cvec_to_faces_kernel<float>, grid, dim3(kBlock), 0, s, g, sb, (const float*)field, fstride,
-                           (WComp3<float>{{(float*)out[0], (float*)out[1], (float*)out[2]}}));
+    with_dtype(v, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(cvec_to_faces_kernel<T>, grid, dim3(kBlock), 0, s, g, sb, (const T*)field, fstride, (WComp3<T>{{(T*)out[0], (T*)out[1], (T*)out[2]}}));
+    });
     PHIHIP_CHECK_HIP(hipGetLastError());
     return PHIHIP_OK;
 }

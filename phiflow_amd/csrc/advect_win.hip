@@ -989,13 +989,14 @@ static int run_win(phihip_ctx* ctx, const GridView& v, const WinCall& call, hipS
             if (v.cn[c][a] < 4 || v.n[a] < 4) return PHIHIP_ERR_UNSUPPORTED;   // a window wider than the axis: the caller keeps the gather kernels
     LaunchScope ls(ctx, PHIHIP_K_ADVECT, s);
     const bool wide = KIND != WK_MC_STAG && call.halo >= 2;           // lookups of the centred kinds reach two cells
-    if (v.dtype == PHIHIP_F64) {
-        if (v.rank == 3) { if (wide) PHIHIP_TRY((launch_win<double, KIND, 3, 8, (KIND != WK_MC_STAG ? 2 : 1)>(ctx, v, g, call, s))); else PHIHIP_TRY((launch_win<double, KIND, 3, 8, 1>(ctx, v, g, call, s))); }
-        else PHIHIP_TRY((launch_win<double, KIND, 2, 8, 1>(ctx, v, g, call, s)));
-    } else {
-        if (v.rank == 3) { if (wide) PHIHIP_TRY((launch_win<float, KIND, 3, 8, (KIND != WK_MC_STAG ? 2 : 1)>(ctx, v, g, call, s))); else PHIHIP_TRY((launch_win<float, KIND, 3, 8, 1>(ctx, v, g, call, s))); }
-        else PHIHIP_TRY((launch_win<float, KIND, 2, 8, 1>(ctx, v, g, call, s)));
-    }
+    PHIHIP_TRY(with_dtype_rank(v, [&](auto t, auto d) {
+        using T = typename decltype(t)::type;
+        constexpr int DIM = decltype(d)::value;
+        if constexpr (DIM == 3) {      // (the two-cell reach exists in 3-D only)
+            if (wide) return launch_win<T, KIND, 3, 8, (KIND != WK_MC_STAG ? 2 : 1)>(ctx, v, g, call, s);
+        }
+        return launch_win<T, KIND, DIM, 8, 1>(ctx, v, g, call, s);
+    }));
     PHIHIP_CHECK_HIP(hipGetLastError());
     return PHIHIP_OK;
 }

@@ -970,7 +970,7 @@ int phihip_make_incompressible(phihip_ctx* ctx, const phihip_grid* grid, void* c
     note_align(v, pressure); note_align(v, div_out); note_align(v, flags, 3u);
     void* div = div_out;
     if (!div) {
-        const size_t bytes = (size_t)v.batch * v.cells * (v.dtype == PHIHIP_F64 ? 8 : 4);
+        const size_t bytes = (size_t)v.batch * v.cells * elem_bytes(v);
         PHIHIP_TRY(ensure_buffer(ctx->ws_rhs, bytes));
         div = ctx->ws_rhs.ptr;
     }
@@ -1409,7 +1409,7 @@ int phihip_curl_2d(phihip_ctx* ctx, const phihip_grid* grid, int staggered, cons
     PHIHIP_REQUIRE(vx && out && s_bc && out != vx && out != vy, "curl_2d: NULL or aliased argument");
     PHIHIP_REQUIRE(staggered ? vy != nullptr : vy == nullptr, "curl_2d: vy must be given for a staggered field and NULL for a centred one");
     PHIHIP_TRY(check_scalar_bc(v, s_bc, "curl_2d"));
-    const void* b = staggered ? vy : (const void*)((const char*)vx + (size_t)v.cells * (v.dtype == PHIHIP_F64 ? 8 : 4));
+    const void* b = staggered ? vy : (const void*)((const char*)vx + (size_t)v.cells * elem_bytes(v));
     return run_curl2d(ctx, v, staggered, s_bc, s_val, 0, vx, b, out, nullptr, s);
 }
 
@@ -1420,7 +1420,7 @@ int phihip_curl_2d_backward(phihip_ctx* ctx, const phihip_grid* grid, int stagge
     PHIHIP_REQUIRE(grad_out && grad_vx && s_bc && grad_out != grad_vx && grad_out != grad_vy, "curl_2d_backward: NULL or aliased argument");
     PHIHIP_REQUIRE(staggered ? grad_vy != nullptr : grad_vy == nullptr, "curl_2d_backward: grad_vy must be given for a staggered field and NULL for a centred one");
     PHIHIP_TRY(check_scalar_bc(v, s_bc, "curl_2d_backward"));
-    void* b = staggered ? grad_vy : (void*)((char*)grad_vx + (size_t)v.cells * (v.dtype == PHIHIP_F64 ? 8 : 4));
+    void* b = staggered ? grad_vy : (void*)((char*)grad_vx + (size_t)v.cells * elem_bytes(v));
     return run_curl2d(ctx, v, staggered, s_bc, nullptr, 1, grad_out, nullptr, grad_vx, b, s);
 }
 

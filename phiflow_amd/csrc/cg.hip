@@ -38,7 +38,7 @@ static PlanKey plan_key(const GridView& v, int mask_batch, bool flags, int famil
 }
 
 int plan_march(const phihip_ctx* ctx, const GridView& v, int mask_batch, bool flags, int family, MarchConfig* c, MarchGrid* g, int force_id) {
-    const int esize = v.dtype == PHIHIP_F64 ? 8 : 4;
+    const int esize = (int)elem_bytes(v);
     const int vmax = 16 / esize;
     memset(g, 0, sizeof(*g));
     g->n0 = v.n[0]; g->n1 = v.n[1]; g->n2 = v.n[2];
@@ -455,13 +455,12 @@ static int laplace_apply_multi_t(phihip_ctx* ctx, const GridView* w, int count, 
 }
 
 int run_laplace_apply_multi(phihip_ctx* ctx, const GridView* w, int count, const void* const* in, void* const* out, hipStream_t s) {
-    return w[0].dtype == PHIHIP_F64 ? laplace_apply_multi_t<double>(ctx, w, count, in, out, s) : laplace_apply_multi_t<float>(ctx, w, count, in, out, s);
+    return with_dtype(w[0], [&](auto t) { return laplace_apply_multi_t<typename decltype(t)::type>(ctx, w, count, in, out, s); });
 }
 
 int run_laplace_apply(phihip_ctx* ctx, const GridView& v, const uint8_t* flags, int mask_batch, const void* p, void* out,
                       hipStream_t s) {
-    return v.dtype == PHIHIP_F64 ? laplace_apply_t<double>(ctx, v, flags, mask_batch, p, out, s)
-                                 : laplace_apply_t<float>(ctx, v, flags, mask_batch, p, out, s);
+    return with_dtype(v, [&](auto t) { return laplace_apply_t<typename decltype(t)::type>(ctx, v, flags, mask_batch, p, out, s); });
 }
 
 long long small_cg_limit(const phihip_ctx* ctx, const GridView& v);
@@ -1312,22 +1311,20 @@ static int slab_update_t(phihip_ctx* ctx, const GridView& v, const uint8_t* flag
 
 int run_slab_residual(phihip_ctx* ctx, const GridView& v, const uint8_t* flags, int mask_batch, const void* x, const void* x_lo, const void* x_hi,
                       const void* rhs, void* r, double* sums, int keep_going, hipStream_t s) {
-    return v.dtype == PHIHIP_F64 ? slab_residual_t<double>(ctx, v, flags, mask_batch, x, x_lo, x_hi, rhs, r, sums, keep_going, s)
-                                 : slab_residual_t<float>(ctx, v, flags, mask_batch, x, x_lo, x_hi, rhs, r, sums, keep_going, s);
+    return with_dtype(v, [&](auto t) { return slab_residual_t<typename decltype(t)::type>(ctx, v, flags, mask_batch, x, x_lo, x_hi, rhs, r, sums, keep_going, s); });
 }
 
 int run_slab_matvec(phihip_ctx* ctx, const GridView& v, const uint8_t* flags, int mask_batch, int first, const double* sums_in, const void* r,
                     const void* r_lo, const void* r_hi, const void* d_old, const void* d_lo, const void* d_hi, void* d_new, double* sum_out,
                     const phihip_solve* solve, hipStream_t s) {
-    return v.dtype == PHIHIP_F64
-               ? slab_matvec_t<double>(ctx, v, flags, mask_batch, first, sums_in, r, r_lo, r_hi, d_old, d_lo, d_hi, d_new, sum_out, solve, s)
-               : slab_matvec_t<float>(ctx, v, flags, mask_batch, first, sums_in, r, r_lo, r_hi, d_old, d_lo, d_hi, d_new, sum_out, solve, s);
+    return with_dtype(v, [&](auto t) {
+        return slab_matvec_t<typename decltype(t)::type>(ctx, v, flags, mask_batch, first, sums_in, r, r_lo, r_hi, d_old, d_lo, d_hi, d_new, sum_out, solve, s);
+    });
 }
 
 int run_slab_update(phihip_ctx* ctx, const GridView& v, const uint8_t* flags, int mask_batch, const double* sum_in, const void* d, const void* d_lo,
                     const void* d_hi, void* x, void* r, double* sum_out, int x_only, const phihip_solve* solve, hipStream_t s) {
-    return v.dtype == PHIHIP_F64 ? slab_update_t<double>(ctx, v, flags, mask_batch, sum_in, d, d_lo, d_hi, x, r, sum_out, x_only, solve, s)
-                                 : slab_update_t<float>(ctx, v, flags, mask_batch, sum_in, d, d_lo, d_hi, x, r, sum_out, x_only, solve, s);
+    return with_dtype(v, [&](auto t) { return slab_update_t<typename decltype(t)::type>(ctx, v, flags, mask_batch, sum_in, d, d_lo, d_hi, x, r, sum_out, x_only, solve, s); });
 }
 
 // folds the last GLOBAL residual sum into the control block and reports it (synchronises the stream)
@@ -1349,8 +1346,7 @@ int run_cg(phihip_ctx* ctx, const GridView& v, const uint8_t* flags, int mask_ba
            const phihip_solve* solve, phihip_solve_info* info, hipStream_t s) {
     // the one place that dispatches on the preconditioner: the single-kernel, resident and single-reduction solvers are not taken with it
     if (solve->method == PHIHIP_METHOD_CG_MULTIGRID) return run_cg_multigrid(ctx, v, flags, mask_batch, rhs, x, solve, info, s);
-    return v.dtype == PHIHIP_F64 ? cg_t<double>(ctx, v, flags, mask_batch, rhs, x, solve, info, nullptr, s)
-                                 : cg_t<float>(ctx, v, flags, mask_batch, rhs, x, solve, info, nullptr, s);
+    return with_dtype(v, [&](auto t) { return cg_t<typename decltype(t)::type>(ctx, v, flags, mask_batch, rhs, x, solve, info, nullptr, s); });
 }
 
 bool cg_uses_marching(const phihip_ctx* ctx, const GridView& v) { return v.op_custom || !(ctx->small_cg && v.cells <= small_cg_limit(ctx, v)); }
@@ -1358,8 +1354,7 @@ bool cg_uses_marching(const phihip_ctx* ctx, const GridView& v) { return v.op_cu
 int run_cg_balancing(phihip_ctx* ctx, const GridView& v, const uint8_t* flags, int mask_batch, void* rhs, void* x, const phihip_solve* solve,
                      phihip_solve_info* info, const double* shift, hipStream_t s) {
     if (solve->method == PHIHIP_METHOD_CG_MULTIGRID) { set_error("cg: the preconditioned solver takes a balanced right-hand side"); return PHIHIP_ERR_BAD_ARG; }
-    return v.dtype == PHIHIP_F64 ? cg_t<double>(ctx, v, flags, mask_batch, rhs, x, solve, info, shift, s)
-                                 : cg_t<float>(ctx, v, flags, mask_batch, rhs, x, solve, info, shift, s);
+    return with_dtype(v, [&](auto t) { return cg_t<typename decltype(t)::type>(ctx, v, flags, mask_batch, rhs, x, solve, info, shift, s); });
 }
 
 }  // namespace phihip

@@ -268,8 +268,7 @@ static int cg_small_t(phihip_ctx* ctx, const GridView& v, const uint8_t* flags, 
 
 int run_cg_small(phihip_ctx* ctx, const GridView& v, const uint8_t* flags, int mask_batch, const void* rhs, void* x,
                  const phihip_solve* solve, void* st_out, hipStream_t s) {
-    return v.dtype == PHIHIP_F64 ? cg_small_t<double>(ctx, v, flags, mask_batch, rhs, x, solve, (CgState*)st_out, s)
-                                 : cg_small_t<float>(ctx, v, flags, mask_batch, rhs, x, solve, (CgState*)st_out, s);
+    return with_dtype(v, [&](auto t) { return cg_small_t<typename decltype(t)::type>(ctx, v, flags, mask_batch, rhs, x, solve, (CgState*)st_out, s); });
 }
 
 }  // namespace phihip

@@ -11,6 +11,7 @@
 #include <array>
 #include <map>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/phihip.h"
@@ -66,6 +67,19 @@ struct GridView {
 };
 
 int make_view(const phihip_grid* grid, GridView* out);
+
+// The one place where the runtime dtype / rank of a view become template arguments (make_view has refused every dtype but F32 / F64):
+//   with_dtype(v, [&](auto t) { using T = typename decltype(t)::type; ... });
+//   with_dtype_rank(v, [&](auto t, auto d) { using T = typename decltype(t)::type; constexpr int DIM = decltype(d)::value; ... });
+// A body that uses PHIHIP_TRY / PHIHIP_REQUIRE / PHIHIP_CHECK_HIP returns int; the caller wraps the call in PHIHIP_TRY or returns it.
+template <typename T> struct TypeTag { using type = T; };
+template <typename F> inline auto with_dtype(const GridView& v, F&& f) {
+    return v.dtype == PHIHIP_F64 ? f(TypeTag<double>{}) : f(TypeTag<float>{});
+}
+template <typename F> inline auto with_dtype_rank(const GridView& v, F&& f) {
+    return with_dtype(v, [&](auto t) { return v.rank == 3 ? f(t, std::integral_constant<int, 3>{}) : f(t, std::integral_constant<int, 2>{}); });
+}
+inline size_t elem_bytes(const GridView& v) { return v.dtype == PHIHIP_F64 ? 8 : 4; }
 
 // by-value kernel parameter describing the staggered layout
 struct VelGrid {

@@ -19,6 +19,7 @@
 // neighbour, a clamped tap returns its weight to the edge sample (T = -G[edge]: the edge sample entered g[edge] with the opposite sign), a
 // constant tap contributes nothing (T = 0). So the gradient's adjoint is cdiv_kernel<T, true> and the divergence's adjoint cgrad_kernel<T, true>:
 // the same marching loops with the sign flipped and the adjoint taps -- NOT the negative divergence / gradient at walls. Gradients accumulate.
+// The run_* launch sites pick the element type with with_dtype (common.hpp); the adjoint / staggered choice stays an `if` inside that lambda.
 #pragma once
 
 namespace phihip {
@@ -318,13 +319,11 @@ int run_cgrad(phihip_ctx* ctx, const GridView& v, const void* in, const int32_t 
     const DiffOp op = diff_op(ctx, v, make_scalar_bc(v, s_bc, s_val));
     LaunchScope ls(ctx, PHIHIP_K_OTHER, s);
     const dim3 grid = diff_grid(op, v.batch);
-    if (v.dtype == PHIHIP_F64) {
-        if (adjoint) hipLaunchKernelGGL((cgrad_kernel<double, true>), grid, dim3(kBlock), 0, s, op, (const double*)in, (double*)out);
-        else hipLaunchKernelGGL((cgrad_kernel<double, false>), grid, dim3(kBlock), 0, s, op, (const double*)in, (double*)out);
-    } else {
-        if (adjoint) hipLaunchKernelGGL((cgrad_kernel<float, true>), grid, dim3(kBlock), 0, s, op, (const float*)in, (float*)out);
-        else hipLaunchKernelGGL((cgrad_kernel<float, false>), grid, dim3(kBlock), 0, s, op, (const float*)in, (float*)out);
-    }
+    with_dtype(v, [&](auto t) {
+        using T = typename decltype(t)::type;
+        if (adjoint) hipLaunchKernelGGL((cgrad_kernel<T, true>), grid, dim3(kBlock), 0, s, op, (const T*)in, (T*)out);
+        else hipLaunchKernelGGL((cgrad_kernel<T, false>), grid, dim3(kBlock), 0, s, op, (const T*)in, (T*)out);
+    });
     PHIHIP_CHECK_HIP(hipGetLastError());
     return PHIHIP_OK;
 }
@@ -335,13 +334,11 @@ int run_cdiv(phihip_ctx* ctx, const GridView& v, const void* in, const int32_t s
     const DiffOp op = diff_op(ctx, v, make_scalar_bc(v, s_bc, s_val));
     LaunchScope ls(ctx, PHIHIP_K_OTHER, s);
     const dim3 grid = diff_grid(op, v.batch);
-    if (v.dtype == PHIHIP_F64) {
-        if (adjoint) hipLaunchKernelGGL((cdiv_kernel<double, true>), grid, dim3(kBlock), 0, s, op, (const double*)in, (double*)out);
-        else hipLaunchKernelGGL((cdiv_kernel<double, false>), grid, dim3(kBlock), 0, s, op, (const double*)in, (double*)out);
-    } else {
-        if (adjoint) hipLaunchKernelGGL((cdiv_kernel<float, true>), grid, dim3(kBlock), 0, s, op, (const float*)in, (float*)out);
-        else hipLaunchKernelGGL((cdiv_kernel<float, false>), grid, dim3(kBlock), 0, s, op, (const float*)in, (float*)out);
-    }
+    with_dtype(v, [&](auto t) {
+        using T = typename decltype(t)::type;
+        if (adjoint) hipLaunchKernelGGL((cdiv_kernel<T, true>), grid, dim3(kBlock), 0, s, op, (const T*)in, (T*)out);
+        else hipLaunchKernelGGL((cdiv_kernel<T, false>), grid, dim3(kBlock), 0, s, op, (const T*)in, (T*)out);
+    });
     PHIHIP_CHECK_HIP(hipGetLastError());
     return PHIHIP_OK;
 }
@@ -382,13 +379,11 @@ int run_curl2d(phihip_ctx* ctx, const GridView& v, int staggered, const int32_t 
     }
     op.tiles1 = ceil_div(ceil_div(op.nx + 1, op.chunk), 4);
     LaunchScope ls(ctx, PHIHIP_K_OTHER, s);
-    if (v.dtype == PHIHIP_F64) {
-        if (staggered) launch_curl<double, true>(op, v.batch, adjoint != 0, a, b, oa, ob, s);
-        else launch_curl<double, false>(op, v.batch, adjoint != 0, a, b, oa, ob, s);
-    } else {
-        if (staggered) launch_curl<float, true>(op, v.batch, adjoint != 0, a, b, oa, ob, s);
-        else launch_curl<float, false>(op, v.batch, adjoint != 0, a, b, oa, ob, s);
-    }
+    with_dtype(v, [&](auto t) {
+        using T = typename decltype(t)::type;
+        if (staggered) launch_curl<T, true>(op, v.batch, adjoint != 0, a, b, oa, ob, s);
+        else launch_curl<T, false>(op, v.batch, adjoint != 0, a, b, oa, ob, s);
+    });
     PHIHIP_CHECK_HIP(hipGetLastError());
     return PHIHIP_OK;
 }
@@ -415,16 +410,13 @@ static int laplace_coef_lattice(phihip_ctx* ctx, const GridView& v, const VelGri
     if (op.cells >= (1LL << 31)) { set_error("laplace: more than 2^31 samples per batch entry are not supported"); return PHIHIP_ERR_UNSUPPORTED; }
     coef_plan(op, 4096);
     LaunchScope ls(ctx, PHIHIP_K_OTHER, s);
-    if (v.dtype == PHIHIP_F64) {
-        CoefArgs<double> a;
+    return with_dtype(v, [&](auto t) {
+        using T = typename decltype(t)::type;
+        CoefArgs<T> a;
         memset(&a, 0, sizeof(a));
-        a.a = (const double*)in; a.o1 = (double*)out; a.accumulate = accumulate;
-        return coef_launch<double, CM_LAP>(op, v.batch, a, s);
-    }
-    CoefArgs<float> a;
-    memset(&a, 0, sizeof(a));
-    a.a = (const float*)in; a.o1 = (float*)out; a.accumulate = accumulate;
-    return coef_launch<float, CM_LAP>(op, v.batch, a, s);
+        a.a = (const T*)in; a.o1 = (T*)out; a.accumulate = accumulate;
+        return coef_launch<T, CM_LAP>(op, v.batch, a, s);
+    });
 }
 
 // laplace of a centred scalar, weights per INTERNAL axis. A uniform weight runs the marching kernels (diffuse.explicit's pass with ident = 0);

@@ -305,16 +305,13 @@ int run_diffuse_coef_explicit(phihip_ctx* ctx, const GridView& v, const void* u,
         for (int a = 0; a < 3; ++a) op.uval[a][0] = op.uval[a][1] = 0.0;
     coef_plan(op, 4096);
     LaunchScope ls(ctx, PHIHIP_K_OTHER, s);
-    if (v.dtype == PHIHIP_F64) {
-        CoefArgs<double> a;
+    return with_dtype(v, [&](auto t) {
+        using T = typename decltype(t)::type;
+        CoefArgs<T> a;
         memset(&a, 0, sizeof(a));
-        a.a = (const double*)u; a.o1 = (double*)out; a.coef = (const double*)coef; a.accumulate = adjoint ? 1 : 0;
-        return coef_launch<double, CM_APPLY>(op, v.batch, a, s);
-    }
-    CoefArgs<float> a;
-    memset(&a, 0, sizeof(a));
-    a.a = (const float*)u; a.o1 = (float*)out; a.coef = (const float*)coef; a.accumulate = adjoint ? 1 : 0;
-    return coef_launch<float, CM_APPLY>(op, v.batch, a, s);
+        a.a = (const T*)u; a.o1 = (T*)out; a.coef = (const T*)coef; a.accumulate = adjoint ? 1 : 0;
+        return coef_launch<T, CM_APPLY>(op, v.batch, a, s);
+    });
 }
 
 // CG on (I + L_a) x = rhs with homogeneous walls, x holds x0 on entry (cg.hip cg_t's two-launch form without the deferred x update)
@@ -454,8 +451,7 @@ int run_diffuse_coef_implicit(phihip_ctx* ctx, const GridView& v, const void* u,
     if (v.cells >= (1LL << 31)) { set_error("diffuse_implicit: more than 2^31 cells per batch entry are not supported"); return PHIHIP_ERR_UNSUPPORTED; }
     if (solve->method == PHIHIP_METHOD_CG_MULTIGRID) { set_error("diffuse_implicit: the multigrid preconditioner covers the pressure solve only"); return PHIHIP_ERR_UNSUPPORTED; }
     const ScalarBc ub = make_scalar_bc(v, s_bc, s_val), cb = make_scalar_bc(v, c_bc, c_val);
-    if (v.dtype == PHIHIP_F64) return diffuse_coef_implicit_t<double>(ctx, v, u, ub, coef, c_batch, cb, kdt, solve, info, out, s);
-    return diffuse_coef_implicit_t<float>(ctx, v, u, ub, coef, c_batch, cb, kdt, solve, info, out, s);
+    return with_dtype(v, [&](auto t) { return diffuse_coef_implicit_t<typename decltype(t)::type>(ctx, v, u, ub, coef, c_batch, cb, kdt, solve, info, out, s); });
 }
 
 }  // namespace phihip

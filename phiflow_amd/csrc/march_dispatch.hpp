@@ -89,8 +89,7 @@ template <> int march_occupancy<double, false>(int id, int vec, int mode, bool f
 template <> int march_occupancy<double, true>(int id, int vec, int mode, bool flags);
 
 inline int march_occupancy_any(const GridView& v, int id, int vec, int mode, bool flags) {
-    if (v.dtype == PHIHIP_F64) return v.rank == 3 ? march_occupancy<double, true>(id, vec, mode, flags) : march_occupancy<double, false>(id, vec, mode, flags);
-    return v.rank == 3 ? march_occupancy<float, true>(id, vec, mode, flags) : march_occupancy<float, false>(id, vec, mode, flags);
+    return with_dtype_rank(v, [&](auto t, auto d) { return march_occupancy<typename decltype(t)::type, decltype(d)::value == 3>(id, vec, mode, flags); });
 }
 
 template <typename T, bool DIM3>

@@ -6,6 +6,7 @@
 // the c-face f (`vel.at(grad)`, phi/field/_resample.py:279-287, 341-364), a missing face taken from the velocity's padding -- along d a face that is
 // not stored is the wall constant or the wrapped face 0, along c the cell beyond the lattice wraps or copies the edge cell.
 // Included by project.hip (the emulation build of the tests compiles the .hip files by name: no translation unit of its own).
+// The run_* functions pick mom_run<T, STAG> with with_dtype (common.hpp): STAG is a constant of the entry point, mom_run picks the rank.
 //
 // THE ARITHMETIC, the same in the 2-D and 3-D instantiations (the rounding count K of tests/momentum_cases.py is counted from it), h_d = (T)(0.5 / dx_d):
 //     g_d = U_c[f + e_d] - U_c[f - e_d]                                    1 rounding
@@ -455,8 +456,7 @@ int run_advect_differential(phihip_ctx* ctx, const GridView& v, const void* cons
         op.bs_v[c] = vel_batch == 1 ? 0 : op.cc[c];
         op.bs_o[c] = op.cc[c];
     }
-    if (v.dtype == PHIHIP_F64) return mom_run<double, true>(ctx, v, op, 0, u, vel, nullptr, out, s);
-    return mom_run<float, true>(ctx, v, op, 0, u, vel, nullptr, out, s);
+    return with_dtype(v, [&](auto t) { return mom_run<typename decltype(t)::type, true>(ctx, v, op, 0, u, vel, nullptr, out, s); });
 }
 
 // gradients accumulate; gu / gv may be NULL (that gradient is not wanted). Every array has v.batch entries.
@@ -468,14 +468,13 @@ int run_advect_differential_bwd(phihip_ctx* ctx, const GridView& v, const void* 
     for (int which = 1; which <= 2; ++which) {
         void* const* o = which == 1 ? gu : gv;
         if (!o) continue;
-        if (v.dtype == PHIHIP_F64) PHIHIP_TRY((mom_run<double, true>(ctx, v, op, which, u, vel, gout, o, s)));
-        else PHIHIP_TRY((mom_run<float, true>(ctx, v, op, which, u, vel, gout, o, s)));
+        PHIHIP_TRY(with_dtype(v, [&](auto t) { return mom_run<typename decltype(t)::type, true>(ctx, v, op, which, u, vel, gout, o, s); }));
     }
     return PHIHIP_OK;
 }
 
 static void mom_split(const GridView& v, const void* base, const void* out[3]) {
-    const size_t es = v.dtype == PHIHIP_F64 ? 8 : 4;
+    const size_t es = elem_bytes(v);
     for (int a = 0; a < 3; ++a) out[a] = (a < v.ax0 || !base) ? nullptr : (const void*)((const char*)base + (size_t)(a - v.ax0) * (size_t)v.cells * es);
 }
 
@@ -495,8 +494,7 @@ int run_advect_differential_centered(phihip_ctx* ctx, const GridView& v, const v
     mom_split(v, vel, pv);
     mom_split(v, out, po);
     void* o[3] = {(void*)po[0], (void*)po[1], (void*)po[2]};
-    if (v.dtype == PHIHIP_F64) return mom_run<double, false>(ctx, v, op, 0, pu, pv, nullptr, o, s);
-    return mom_run<float, false>(ctx, v, op, 0, pu, pv, nullptr, o, s);
+    return with_dtype(v, [&](auto t) { return mom_run<typename decltype(t)::type, false>(ctx, v, op, 0, pu, pv, nullptr, o, s); });
 }
 
 int run_advect_differential_centered_bwd(phihip_ctx* ctx, const GridView& v, const void* u, const int32_t s_bc[3][2], const double s_val[3][2], const void* vel,
@@ -514,8 +512,7 @@ int run_advect_differential_centered_bwd(phihip_ctx* ctx, const GridView& v, con
         if (!dst) continue;
         mom_split(v, dst, po);
         void* o[3] = {(void*)po[0], (void*)po[1], (void*)po[2]};
-        if (v.dtype == PHIHIP_F64) PHIHIP_TRY((mom_run<double, false>(ctx, v, op, which, pu, pv, pg, o, s)));
-        else PHIHIP_TRY((mom_run<float, false>(ctx, v, op, which, pu, pv, pg, o, s)));
+        PHIHIP_TRY(with_dtype(v, [&](auto t) { return mom_run<typename decltype(t)::type, false>(ctx, v, op, which, pu, pv, pg, o, s); }));
     }
     return PHIHIP_OK;
 }

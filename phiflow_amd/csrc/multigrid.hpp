@@ -763,7 +763,7 @@ static int mg_apply_t(phihip_ctx* ctx, const GridView& v, const uint8_t* flags, 
 
 int run_multigrid_apply(phihip_ctx* ctx, const GridView& v, const uint8_t* flags, int mask_batch, const void* r, void* z, hipStream_t s) {
     if (v.op_custom || v.halo[0] || v.halo[1]) { set_error("multigrid: only the pressure operator of an undivided grid is covered"); return PHIHIP_ERR_UNSUPPORTED; }
-    return v.dtype == PHIHIP_F64 ? mg_apply_t<double>(ctx, v, flags, mask_batch, r, z, s) : mg_apply_t<float>(ctx, v, flags, mask_batch, r, z, s);
+    return with_dtype(v, [&](auto t) { return mg_apply_t<typename decltype(t)::type>(ctx, v, flags, mask_batch, r, z, s); });
 }
 
 template <typename T, int MODE>
@@ -888,8 +888,10 @@ int run_cg_multigrid(phihip_ctx* ctx, const GridView& v, const uint8_t* flags, i
         set_error("the multigrid preconditioner covers the pressure solve only (not diffuse.implicit, shifted operators or slab-decomposed solves)");
         return PHIHIP_ERR_UNSUPPORTED;
     }
-    return v.dtype == PHIHIP_F64 ? mg_cg_t<double>(ctx, v, flags, mask_batch, (const double*)rhs, (double*)x, solve, info, s)
-                                 : mg_cg_t<float>(ctx, v, flags, mask_batch, (const float*)rhs, (float*)x, solve, info, s);
+    return with_dtype(v, [&](auto t) {
+        using T = typename decltype(t)::type;
+        return mg_cg_t<T>(ctx, v, flags, mask_batch, (const T*)rhs, (T*)x, solve, info, s);
+    });
 }
 
 }  // namespace phihip

@@ -248,13 +248,11 @@ static int run_sdf_apply(phihip_ctx* ctx, const GridView& v, const phihip_obstac
     pb.first[3] = (int)total;
     if (total == 0) return PHIHIP_OK;
     const int nblk = total < 4096 ? (int)total : 4096;
-    if (v.dtype == PHIHIP_F64) {
-        Comp3<double> c{{(double*)vel[0], (double*)vel[1], (double*)vel[2]}};
-        hipLaunchKernelGGL(sdf_apply_kernel<double>, dim3(nblk, v.batch), dim3(kBlock), 0, s, g, v.lower[0], v.lower[1], v.lower[2], w, pb, c);
-    } else {
-        Comp3<float> c{{(float*)vel[0], (float*)vel[1], (float*)vel[2]}};
-        hipLaunchKernelGGL(sdf_apply_kernel<float>, dim3(nblk, v.batch), dim3(kBlock), 0, s, g, v.lower[0], v.lower[1], v.lower[2], w, pb, c);
-    }
+    with_dtype(v, [&](auto t) {
+        using T = typename decltype(t)::type;
+        Comp3<T> c{{(T*)vel[0], (T*)vel[1], (T*)vel[2]}};
+        hipLaunchKernelGGL(sdf_apply_kernel<T>, dim3(nblk, v.batch), dim3(kBlock), 0, s, g, v.lower[0], v.lower[1], v.lower[2], w, pb, c);
+    });
     return PHIHIP_OK;
 }
 

@@ -349,15 +349,12 @@ int run_balance(phihip_ctx* ctx, const GridView& v, const uint8_t* flags, int ma
     const int fpb = mask_batch > 1 ? 1 : 0;
     LaunchScope ls(ctx, PHIHIP_K_DIVERGENCE, s);
     const int nb2 = ceil_div(v.cells, kBlock) < 8192 ? ceil_div(v.cells, kBlock) : 8192;
-    if (v.dtype == PHIHIP_F64) {
-        hipLaunchKernelGGL(sum_cells_kernel<double>, dim3(nblk, v.batch), dim3(kBlock), 0, s, (const double*)x, flags, fpb, v.cells, part_sum, part_act, nblk);
+    with_dtype(v, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(sum_cells_kernel<T>, dim3(nblk, v.batch), dim3(kBlock), 0, s, (const T*)x, flags, fpb, v.cells, part_sum, part_act, nblk);
         hipLaunchKernelGGL(balance_scalar_kernel, dim3(v.batch), dim3(kBlock), 0, s, (const double*)part_sum, (const double*)part_act, nblk, shift);
-        hipLaunchKernelGGL(balance_apply_kernel<double>, dim3(nb2, v.batch), dim3(kBlock), 0, s, (double*)x, flags, fpb, (const double*)shift, v.cells);
-    } else {
-        hipLaunchKernelGGL(sum_cells_kernel<float>, dim3(nblk, v.batch), dim3(kBlock), 0, s, (const float*)x, flags, fpb, v.cells, part_sum, part_act, nblk);
-        hipLaunchKernelGGL(balance_scalar_kernel, dim3(v.batch), dim3(kBlock), 0, s, (const double*)part_sum, (const double*)part_act, nblk, shift);
-        hipLaunchKernelGGL(balance_apply_kernel<float>, dim3(nb2, v.batch), dim3(kBlock), 0, s, (float*)x, flags, fpb, (const double*)shift, v.cells);
-    }
+        hipLaunchKernelGGL(balance_apply_kernel<T>, dim3(nb2, v.batch), dim3(kBlock), 0, s, (T*)x, flags, fpb, (const double*)shift, v.cells);
+    });
     PHIHIP_CHECK_HIP(hipGetLastError());
     return PHIHIP_OK;
 }
@@ -418,13 +415,9 @@ int run_divergence(phihip_ctx* ctx, const GridView& v, const void* const vel[3],
     int nblk = 0;
     {
         LaunchScope ls(ctx, PHIHIP_K_DIVERGENCE, s);
-        if (v.dtype == PHIHIP_F64) {
-            if (v.rank == 3) PHIHIP_TRY((launch_divergence<double, 3>(ctx, v, g, vel, flags, fpb, div, finite_guard, &nblk, s)));
-            else PHIHIP_TRY((launch_divergence<double, 2>(ctx, v, g, vel, flags, fpb, div, finite_guard, &nblk, s)));
-        } else {
-            if (v.rank == 3) PHIHIP_TRY((launch_divergence<float, 3>(ctx, v, g, vel, flags, fpb, div, finite_guard, &nblk, s)));
-            else PHIHIP_TRY((launch_divergence<float, 2>(ctx, v, g, vel, flags, fpb, div, finite_guard, &nblk, s)));
-        }
+        PHIHIP_TRY(with_dtype_rank(v, [&](auto t, auto d) {
+            return launch_divergence<typename decltype(t)::type, decltype(d)::value>(ctx, v, g, vel, flags, fpb, div, finite_guard, &nblk, s);
+        }));
     }
     double* part_sum = (double*)ctx->ws_div.ptr;
     double* part_act = part_sum + (size_t)v.batch * nblk;
@@ -438,12 +431,10 @@ int run_divergence(phihip_ctx* ctx, const GridView& v, const void* const vel[3],
             return PHIHIP_OK;
         }
         const int nb2 = ceil_div(v.cells, kBlock) < 8192 ? ceil_div(v.cells, kBlock) : 8192;
-        if (v.dtype == PHIHIP_F64)
-            hipLaunchKernelGGL(balance_apply_kernel<double>, dim3(nb2, v.batch), dim3(kBlock), 0, s, (double*)div, flags, fpb,
-                               (const double*)shift, v.cells);
-        else
-            hipLaunchKernelGGL(balance_apply_kernel<float>, dim3(nb2, v.batch), dim3(kBlock), 0, s, (float*)div, flags, fpb,
-                               (const double*)shift, v.cells);
+        with_dtype(v, [&](auto t) {
+            using T = typename decltype(t)::type;
+            hipLaunchKernelGGL(balance_apply_kernel<T>, dim3(nb2, v.batch), dim3(kBlock), 0, s, (T*)div, flags, fpb, (const double*)shift, v.cells);
+        });
     }
     PHIHIP_CHECK_HIP(hipGetLastError());
     return PHIHIP_OK;
@@ -647,13 +638,7 @@ int run_grad_subtract(phihip_ctx* ctx, const GridView& v, const uint8_t* flags, 
     const VelGrid g = make_velgrid(v);
     const int fpb = mask_batch > 1 ? 1 : 0;
     LaunchScope ls(ctx, PHIHIP_K_GRAD_SUBTRACT, s);
-    if (v.dtype == PHIHIP_F64) {
-        if (v.rank == 3) launch_grad_subtract<double, 3>(v, g, flags, fpb, p, vel, s);
-        else launch_grad_subtract<double, 2>(v, g, flags, fpb, p, vel, s);
-    } else {
-        if (v.rank == 3) launch_grad_subtract<float, 3>(v, g, flags, fpb, p, vel, s);
-        else launch_grad_subtract<float, 2>(v, g, flags, fpb, p, vel, s);
-    }
+    with_dtype_rank(v, [&](auto t, auto d) { launch_grad_subtract<typename decltype(t)::type, decltype(d)::value>(v, g, flags, fpb, p, vel, s); });
     PHIHIP_CHECK_HIP(hipGetLastError());
     return PHIHIP_OK;
 }
@@ -675,12 +660,10 @@ int run_scale_faces(phihip_ctx* ctx, const GridView& v, void* const vel[3], cons
     LaunchScope ls(ctx, PHIHIP_K_OTHER, s);
     for (int ca = v.ax0; ca < 3; ++ca) {
         const int nblk = ceil_div(v.ccells[ca], kBlock) < 8192 ? ceil_div(v.ccells[ca], kBlock) : 8192;
-        if (v.dtype == PHIHIP_F64)
-            hipLaunchKernelGGL(scale_kernel<double>, dim3(nblk, v.batch), dim3(kBlock), 0, s, (double*)vel[ca], (const double*)m[ca],
-                               v.ccells[ca], 0);
-        else
-            hipLaunchKernelGGL(scale_kernel<float>, dim3(nblk, v.batch), dim3(kBlock), 0, s, (float*)vel[ca], (const float*)m[ca],
-                               v.ccells[ca], 0);
+        with_dtype(v, [&](auto t) {
+            using T = typename decltype(t)::type;
+            hipLaunchKernelGGL(scale_kernel<T>, dim3(nblk, v.batch), dim3(kBlock), 0, s, (T*)vel[ca], (const T*)m[ca], v.ccells[ca], 0);
+        });
     }
     PHIHIP_CHECK_HIP(hipGetLastError());
     return PHIHIP_OK;
@@ -852,9 +835,9 @@ int run_centered_to_staggered(phihip_ctx* ctx, const GridView& v, const void* sf
     const ScalarBc sb = make_scalar_bc(v, s_bc, s_val);
     LaunchScope ls(ctx, PHIHIP_K_OTHER, s);
     {
-        bool done;
-        if (v.dtype == PHIHIP_F64) done = v.rank == 3 ? launch_c2s_vec<double, 3>(v, g, sb, sfield, vector, accumulate, out, s) : launch_c2s_vec<double, 2>(v, g, sb, sfield, vector, accumulate, out, s);
-        else done = v.rank == 3 ? launch_c2s_vec<float, 3>(v, g, sb, sfield, vector, accumulate, out, s) : launch_c2s_vec<float, 2>(v, g, sb, sfield, vector, accumulate, out, s);
+        const bool done = with_dtype_rank(v, [&](auto t, auto d) {
+            return launch_c2s_vec<typename decltype(t)::type, decltype(d)::value>(v, g, sb, sfield, vector, accumulate, out, s);
+        });
         if (done) {
             PHIHIP_CHECK_HIP(hipGetLastError());
             return PHIHIP_OK;
@@ -863,12 +846,11 @@ int run_centered_to_staggered(phihip_ctx* ctx, const GridView& v, const void* sf
     for (int ca = v.ax0; ca < 3; ++ca) {      // rows that are not whole vectors / unaligned buffers: one scalar launch per component
         if (accumulate && vector[ca] == 0.0) continue;   // adding 0 * s leaves the component as it is
         const int nblk = ceil_div(v.ccells[ca], kBlock) < 16384 ? ceil_div(v.ccells[ca], kBlock) : 16384;
-        if (v.dtype == PHIHIP_F64)
-            hipLaunchKernelGGL(centered_to_staggered_kernel<double>, dim3(nblk, v.batch), dim3(kBlock), 0, s, g, sb, ca, (const double*)sfield,
-                               (double*)out[ca], vector[ca], accumulate);
-        else
-            hipLaunchKernelGGL(centered_to_staggered_kernel<float>, dim3(nblk, v.batch), dim3(kBlock), 0, s, g, sb, ca, (const float*)sfield,
-                               (float*)out[ca], (float)vector[ca], accumulate);
+        with_dtype(v, [&](auto t) {
+            using T = typename decltype(t)::type;
+            hipLaunchKernelGGL(centered_to_staggered_kernel<T>, dim3(nblk, v.batch), dim3(kBlock), 0, s, g, sb, ca, (const T*)sfield, (T*)out[ca], (T)vector[ca],
+                               accumulate);
+        });
     }
     PHIHIP_CHECK_HIP(hipGetLastError());
     return PHIHIP_OK;
@@ -1288,13 +1270,11 @@ int run_apply_obstacles(phihip_ctx* ctx, const GridView& v, const phihip_obstacl
         pb.first[3] = (int)total;
         if (total == 0) continue;
         const int nblk = total < 4096 ? (int)total : 4096;
-        if (v.dtype == PHIHIP_F64) {
-            Comp3<double> c{{(double*)vel[0], (double*)vel[1], (double*)vel[2]}};
-            hipLaunchKernelGGL(apply_obstacles_kernel<double>, dim3(nblk, v.batch), dim3(kBlock), 0, s, g, v.lower[0], v.lower[1], v.lower[2], set, pb, c);
-        } else {
-            Comp3<float> c{{(float*)vel[0], (float*)vel[1], (float*)vel[2]}};
-            hipLaunchKernelGGL(apply_obstacles_kernel<float>, dim3(nblk, v.batch), dim3(kBlock), 0, s, g, v.lower[0], v.lower[1], v.lower[2], set, pb, c);
-        }
+        with_dtype(v, [&](auto t) {
+            using T = typename decltype(t)::type;
+            Comp3<T> c{{(T*)vel[0], (T*)vel[1], (T*)vel[2]}};
+            hipLaunchKernelGGL(apply_obstacles_kernel<T>, dim3(nblk, v.batch), dim3(kBlock), 0, s, g, v.lower[0], v.lower[1], v.lower[2], set, pb, c);
+        });
     }
     PHIHIP_CHECK_HIP(hipGetLastError());
     return PHIHIP_OK;
@@ -1671,8 +1651,10 @@ static int diffuse_affine_walls(phihip_ctx* ctx, const GridView& v, const VelGri
             const double add = kdt * g.bcv[a][side][ca] * g.rdx[a] * g.rdx[a];
             const long long total = g.ccells[ca] / g.cn[ca][a];
             const dim3 grid((unsigned)((total + kBlock - 1) / kBlock < 4096 ? (total + kBlock - 1) / kBlock : 4096), v.batch);
-            if (v.dtype == PHIHIP_F64) hipLaunchKernelGGL(affine_walls_kernel<double>, grid, dim3(kBlock), 0, s, g, ca, a, side, (double*)out, add);
-            else hipLaunchKernelGGL(affine_walls_kernel<float>, grid, dim3(kBlock), 0, s, g, ca, a, side, (float*)out, (float)add);
+            with_dtype(v, [&](auto t) {
+                using T = typename decltype(t)::type;
+                hipLaunchKernelGGL(affine_walls_kernel<T>, grid, dim3(kBlock), 0, s, g, ca, a, side, (T*)out, (T)add);
+            });
         }
     PHIHIP_CHECK_HIP(hipGetLastError());
     return PHIHIP_OK;
@@ -1716,8 +1698,7 @@ int run_diffuse_bwd(phihip_ctx* ctx, const GridView& v, const void* const gout[3
     LaunchScope ls(ctx, PHIHIP_K_OTHER, s);
     for (int ca = v.ax0; ca < 3; ++ca) {
         if (v.ccells[ca] >= (1LL << 31)) { set_error("diffuse: more than 2^31 samples per component and batch entry are not supported"); return PHIHIP_ERR_UNSUPPORTED; }
-        if (v.dtype == PHIHIP_F64) launch_diffuse<double, true>(g, ca, v.batch, gout[ca], gin[ca], kdt, s);
-        else launch_diffuse<float, true>(g, ca, v.batch, gout[ca], gin[ca], kdt, s);
+        with_dtype(v, [&](auto t) { launch_diffuse<typename decltype(t)::type, true>(g, ca, v.batch, gout[ca], gin[ca], kdt, s); });
     }
     PHIHIP_CHECK_HIP(hipGetLastError());
     return PHIHIP_OK;
@@ -1746,8 +1727,7 @@ int run_diffuse_centered(phihip_ctx* ctx, const GridView& v, const void* sfield,
     if (v.cells >= (1LL << 31)) { set_error("diffuse: more than 2^31 cells per batch entry are not supported"); return PHIHIP_ERR_UNSUPPORTED; }
     if (!adjoint) return diffuse_explicit_lattice(ctx, v, g, 2, sfield, out, kdt, s);
     LaunchScope ls(ctx, PHIHIP_K_OTHER, s);
-    if (v.dtype == PHIHIP_F64) launch_diffuse<double, true>(g, 2, v.batch, sfield, out, kdt, s);
-    else launch_diffuse<float, true>(g, 2, v.batch, sfield, out, kdt, s);
+    with_dtype(v, [&](auto t) { launch_diffuse<typename decltype(t)::type, true>(g, 2, v.batch, sfield, out, kdt, s); });
     PHIHIP_CHECK_HIP(hipGetLastError());
     return PHIHIP_OK;
 }
@@ -1784,16 +1764,17 @@ static int diffuse_implicit_lattice(phihip_ctx* ctx, const GridView& v, const Ve
     bool affine;
     const GridView w = lattice_view(v, g, ca, 1.0, -kdt, &affine);
     if (w.cells >= (1LL << 31)) { set_error("diffuse_implicit: more than 2^31 samples per batch entry are not supported"); return PHIHIP_ERR_UNSUPPORTED; }
-    const size_t esize = v.dtype == PHIHIP_F64 ? 8 : 4;
-    const size_t bytes = (size_t)v.batch * w.cells * esize;
+    const size_t bytes = (size_t)v.batch * w.cells * elem_bytes(v);
     const void* rhs = in;
     if (affine) {
         PHIHIP_TRY(ensure_buffer(ctx->ws_adj_q, bytes));
         LaunchScope ls(ctx, PHIHIP_K_OTHER, s);
         const long long nb = (w.cells + kBlock - 1) / kBlock;
         const dim3 grid((unsigned)(nb < 65536 ? nb : 65536), v.batch);
-        if (v.dtype == PHIHIP_F64) hipLaunchKernelGGL(implicit_rhs_kernel<double>, grid, dim3(kBlock), 0, s, g, ca, (const double*)in, (double*)ctx->ws_adj_q.ptr, kdt);
-        else hipLaunchKernelGGL(implicit_rhs_kernel<float>, grid, dim3(kBlock), 0, s, g, ca, (const float*)in, (float*)ctx->ws_adj_q.ptr, (float)kdt);
+        with_dtype(v, [&](auto t) {
+            using T = typename decltype(t)::type;
+            hipLaunchKernelGGL(implicit_rhs_kernel<T>, grid, dim3(kBlock), 0, s, g, ca, (const T*)in, (T*)ctx->ws_adj_q.ptr, (T)kdt);
+        });
         PHIHIP_CHECK_HIP(hipGetLastError());
         rhs = ctx->ws_adj_q.ptr;
     }
