@@ -457,3 +457,4 @@ int run_cg_balancing(phihip_ctx*, const GridView&, const uint8_t* flags, int mas
                      const double* shift, hipStream_t);
 
 }  // namespace phihip
+#include "column_march.hpp"   // needs xcd_order's neighbours above: kBlock (stencil_march.hpp), ceil_div, set_error

@@ -8,7 +8,7 @@
 // U = the field padded by one sample with its own extrapolation: PERIODIC wraps, OPEN (zero-gradient) copies the edge sample, CLOSED is the
 // constant. Included by project.hip (the emulation build of the tests compiles the .hip files by name: no translation unit of its own).
 //
-// cgrad / cdiv: a 256-thread workgroup owns a (4 rows x 64 columns) column of cells and marches over a chunk of a0 planes like diffuse_kernel:
+// cgrad / cdiv: column-march kernels (column_march.hpp: launch plan and tile decode) like diffuse_kernel:
 // the a0 neighbours are the values the thread read one plane earlier / reads one plane ahead (registers), the in-plane taps and their boundary
 // rule are resolved once per thread. Every input array is read from HBM once, every output written once; all components and batch entries in
 // one launch. curl2d: a 2-D grid has one a0 plane, so the forward kernel marches over the ROWS: every wavefront of the (4 x 64) workgroup owns 64
@@ -32,7 +32,7 @@ struct DiffOp {
     int bc[3][2];          // the field's extrapolation per internal axis / side (unused axis: periodic)
     double val[3][2];
     double w[3];           // 1 / (2 dx_a), 0 on the unused axis
-    int tiles1, tiles2, chunk;
+    ColumnPlan plan;
 };
 
 // value of a tap that falls outside the array: rule 1 = zero-gradient, 2 = constant (0 = inside / wrapped: `loaded`)
@@ -79,15 +79,9 @@ __device__ __forceinline__ T diff_plane_nb(const DiffOp& op, const T* __restrict
 #define PHIHIP_DIFF_TILE_PROLOGUE                                                                   \
     const int b = blockIdx.y;                                                                       \
     const int n0 = op.n[0], n1 = op.n[1], n2 = op.n[2];                                             \
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;                                         \
-    const int bid = xcd_order(blockIdx.x, gridDim.x);                                               \
-    const int t2 = bid % op.tiles2;                                                                 \
-    const int t1 = (bid / op.tiles2) % op.tiles1;                                                   \
-    const int ch = bid / (op.tiles2 * op.tiles1);                                                   \
-    const int i1 = t1 * 4 + ty, i2 = t2 * 64 + tx;                                                  \
-    if (i1 >= n1 || i2 >= n2) return;                                                               \
-    const int p0 = ch * op.chunk, p1 = p0 + op.chunk < n0 ? p0 + op.chunk : n0;                     \
-    if (p0 >= p1) return;                                                                           \
+    ColumnTile ct = column_tile(op.plan, n1, n2, xcd_order(blockIdx.x, gridDim.x));                 \
+    if (!ct.inside || !column_planes(op.plan, ct, n0)) return;                                      \
+    const int i1 = ct.i1, i2 = ct.i2, p0 = ct.p0, p1 = ct.p1;                                       \
     T w[3];                                                                                         \
     _Pragma("unroll") for (int ax = 0; ax < 3; ++ax) w[ax] = (T)op.w[ax];                           \
     int off[4], rule[4];                                                                            \
@@ -279,8 +273,7 @@ __global__ __launch_bounds__(kBlock) void curl2d_kernel(CurlOp op, const T* __re
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------------------
 // planes per workgroup: phihip_set_tuning_kernel(ctx, 0, ., ., chunk) -- the family of the apply-type stencils -- wins over the plan when chunk > 0
-static DiffOp diff_op(const phihip_ctx* ctx, const GridView& v, const ScalarBc& sb) {
-    DiffOp op;
+static int diff_op(const phihip_ctx* ctx, const GridView& v, const ScalarBc& sb, DiffOp& op) {
     memset(&op, 0, sizeof(op));
     op.ax0 = v.ax0;
     op.comps = 3 - v.ax0;
@@ -293,18 +286,11 @@ static DiffOp diff_op(const phihip_ctx* ctx, const GridView& v, const ScalarBc& 
             op.val[a][side] = a < v.ax0 ? 0.0 : sb.val[a][side];
         }
     }
-    op.tiles1 = ceil_div(op.n[1], 4);
-    op.tiles2 = ceil_div(op.n[2], 64);
-    const long long tiles = (long long)op.tiles1 * op.tiles2;
-    int chunks = (int)((4096 + tiles - 1) / tiles);                     // ~4096 workgroups per batch entry when the grid allows
-    chunks = chunks > op.n[0] ? op.n[0] : (chunks < 1 ? 1 : chunks);
-    op.chunk = ceil_div(op.n[0], chunks);
-    if (ctx->tuning[0].chunk > 0) op.chunk = ctx->tuning[0].chunk < op.n[0] ? ctx->tuning[0].chunk : op.n[0];
-    return op;
+    return plan_columns(op.n, kPatchRows, kPatchCols, 4096, ctx->tuning[0].chunk, false, "centred gradient / divergence", op.plan);      // ~4096 workgroups per batch entry when the grid allows
 }
 
 static inline dim3 diff_grid(const DiffOp& op, int batch) {
-    return dim3((unsigned)((long long)op.tiles1 * op.tiles2 * ceil_div(op.n[0], op.chunk)), batch);
+    return dim3((unsigned)((long long)op.plan.tiles1 * op.plan.tiles2 * op.plan.chunks), batch);
 }
 
 static int diff_check(const GridView& v, const char* what) {
@@ -316,7 +302,8 @@ static int diff_check(const GridView& v, const char* what) {
 // one scalar -> components: the centred gradient (adjoint == 0) or the adjoint of the centred divergence (accumulated)
 int run_cgrad(phihip_ctx* ctx, const GridView& v, const void* in, const int32_t s_bc[3][2], const double s_val[3][2], void* out, int adjoint, hipStream_t s) {
     PHIHIP_TRY(diff_check(v, adjoint ? "divergence_centered_backward" : "gradient_centered"));
-    const DiffOp op = diff_op(ctx, v, make_scalar_bc(v, s_bc, s_val));
+    DiffOp op;
+    PHIHIP_TRY(diff_op(ctx, v, make_scalar_bc(v, s_bc, s_val), op));
     LaunchScope ls(ctx, PHIHIP_K_OTHER, s);
     const dim3 grid = diff_grid(op, v.batch);
     with_dtype(v, [&](auto t) {
@@ -331,7 +318,8 @@ int run_cgrad(phihip_ctx* ctx, const GridView& v, const void* in, const int32_t 
 // components -> one scalar: the centred divergence (adjoint == 0) or the adjoint of the centred gradient (accumulated)
 int run_cdiv(phihip_ctx* ctx, const GridView& v, const void* in, const int32_t s_bc[3][2], const double s_val[3][2], void* out, int adjoint, hipStream_t s) {
     PHIHIP_TRY(diff_check(v, adjoint ? "gradient_centered_backward" : "divergence_centered"));
-    const DiffOp op = diff_op(ctx, v, make_scalar_bc(v, s_bc, s_val));
+    DiffOp op;
+    PHIHIP_TRY(diff_op(ctx, v, make_scalar_bc(v, s_bc, s_val), op));
     LaunchScope ls(ctx, PHIHIP_K_OTHER, s);
     const dim3 grid = diff_grid(op, v.batch);
     with_dtype(v, [&](auto t) {
@@ -408,7 +396,7 @@ static int laplace_coef_lattice(phihip_ctx* ctx, const GridView& v, const VelGri
         }
     }
     if (op.cells >= (1LL << 31)) { set_error("laplace: more than 2^31 samples per batch entry are not supported"); return PHIHIP_ERR_UNSUPPORTED; }
-    coef_plan(op, 4096);
+    PHIHIP_TRY(coef_plan(op, 4096, "laplace"));
     LaunchScope ls(ctx, PHIHIP_K_OTHER, s);
     return with_dtype(v, [&](auto t) {
         using T = typename decltype(t)::type;

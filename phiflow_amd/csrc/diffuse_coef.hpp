@@ -20,8 +20,8 @@
 //    but not in implicit (min(-|w| a, 0) = -|w| a). Read from the reference's code, not run against PhiML.
 // Without a coefficient array (a == 1) the operator is the per-axis weighted Laplacian of laplace(u, weights=k) (diffuse.py:140-141).
 //
-// Kernels: a 256-thread workgroup owns a (4 rows x 64 columns) column of cells and marches over a chunk of a0 planes like diffuse_kernel
-// (project.hip): the a0 neighbours of u and of the coefficient are the values the thread read one plane earlier / reads one plane ahead
+// Kernels: a column march (column_march.hpp: plan and tile decode; the tap block below resolves u's rule and the coefficient's in one pass and
+// is this kernel's own) like diffuse_kernel (project.hip): the a0 neighbours of u and of the coefficient are the values the thread read one plane earlier / reads one plane ahead
 // (registers), the in-plane neighbours are the neighbouring lanes' loads of the same plane (L1 / L2 hits). Every array is read from HBM once
 // per launch: explicit = u + a in, out written, 12 B per cell in fp32.
 // CG (same semantics as cg.hip cg_t: 'CG' and 'CG-adaptive', rtol / atol, max_iterations, refresh every `refresh_every` like PhiML, tolerance
@@ -55,7 +55,8 @@ struct CoefOp {
     double w[3];           // signed k_d dt' / dx_d^2 (0 on unused axes)
     int has_c;             // 0: no coefficient array (a == 1)
     int c_per_batch;       // 1: the coefficient has u's batch, 0: one array for every batch entry
-    int tiles1, tiles2, chunk, nblk;
+    ColumnPlan plan;
+    int nblk;              // workgroups = partial sums per batch entry
 };
 
 template <typename T>
@@ -94,14 +95,10 @@ __global__ __launch_bounds__(kBlock) void coef_kernel(CoefOp op, CoefArgs<T> p) 
         alpha = (T)S.alpha;
         beta = (T)S.beta;
     }
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-    const int bid = xcd_order(blockIdx.x, gridDim.x);        // neighbouring columns share an XCD's L2 (their halo rows / columns)
-    const int t2 = bid % op.tiles2;
-    const int t1 = (bid / op.tiles2) % op.tiles1;
-    const int ch = bid / (op.tiles2 * op.tiles1);
-    const int i1 = t1 * 4 + ty, i2 = t2 * 64 + tx;
-    const int p0 = ch * op.chunk, p1 = p0 + op.chunk < n0 ? p0 + op.chunk : n0;
-    const bool active = i1 < n1 && i2 < n2 && p0 < p1;      // (inactive threads still take part in the block reductions)
+    // (neighbouring columns share an XCD's L2: their halo rows / columns; inactive threads still take part in the block reductions)
+    ColumnTile t = column_tile(op.plan, n1, n2, xcd_order(blockIdx.x, gridDim.x));
+    const bool active = column_planes(op.plan, t, n0) && t.inside;
+    const int i1 = t.i1, i2 = t.i2, p0 = t.p0, p1 = t.p1;
     const T* __restrict__ A = p.a + bb;
     const T* __restrict__ B = p.b ? p.b + bb : nullptr;
     const T* __restrict__ C = op.has_c ? p.coef + (op.c_per_batch ? bb : 0) : nullptr;
@@ -254,16 +251,11 @@ __global__ __launch_bounds__(kBlock) void coef_state_kernel(int kind, const CgSt
     cg_prologue(kind, st_in, st_out, pin1, pin2, nblk, prm, blockIdx.x, true, red, &sh);
 }
 
-// launch geometry: (4 x 64)-cell columns, a0 split into chunks so that a batch entry has about `target` workgroups
-static inline void coef_plan(CoefOp& op, int target) {
-    op.tiles1 = (op.n[1] + 3) / 4;
-    op.tiles2 = (op.n[2] + 63) / 64;
-    const long long tiles = (long long)op.tiles1 * op.tiles2;
-    int chunks = (int)((target + tiles - 1) / tiles);
-    chunks = chunks > op.n[0] ? op.n[0] : (chunks < 1 ? 1 : chunks);
-    op.chunk = (op.n[0] + chunks - 1) / chunks;
-    chunks = (op.n[0] + op.chunk - 1) / op.chunk;
-    op.nblk = (int)(tiles * chunks);
+// launch geometry: about `target` workgroups per batch entry (column_march.hpp)
+static inline int coef_plan(CoefOp& op, int target, const char* what) {
+    PHIHIP_TRY(plan_columns(op.n, kPatchRows, kPatchCols, target, 0, false, what, op.plan));
+    op.nblk = op.plan.tiles1 * op.plan.tiles2 * op.plan.chunks;
+    return PHIHIP_OK;
 }
 
 template <typename T, int MODE>
@@ -303,7 +295,7 @@ int run_diffuse_coef_explicit(phihip_ctx* ctx, const GridView& v, const void* u,
     CoefOp op = coef_op(v, ub, coef, c_batch, cb, kdt, 1.0);
     if (adjoint)
         for (int a = 0; a < 3; ++a) op.uval[a][0] = op.uval[a][1] = 0.0;
-    coef_plan(op, 4096);
+    PHIHIP_TRY(coef_plan(op, 4096, "diffuse"));
     LaunchScope ls(ctx, PHIHIP_K_OTHER, s);
     return with_dtype(v, [&](auto t) {
         using T = typename decltype(t)::type;
@@ -319,7 +311,7 @@ template <typename T>
 static int coef_cg_t(phihip_ctx* ctx, const CoefOp& op0, int batch, const T* coef, const T* rhs, T* x, const phihip_solve* solve,
                      phihip_solve_info* info, hipStream_t s) {
     CoefOp op = op0;
-    coef_plan(op, 1024);      // (fewer workgroups than the explicit pass: every workgroup of the next launch re-reduces all partials)
+    PHIHIP_TRY(coef_plan(op, 1024, "diffuse_implicit"));      // (fewer workgroups than the explicit pass: every workgroup of the next launch re-reduces all partials)
     const size_t vec_bytes = (size_t)batch * op.cells * sizeof(T);
     const size_t part_n = (size_t)batch * op.nblk;
     PHIHIP_TRY(ensure_buffer(ctx->ws_coef_r, vec_bytes));
@@ -432,7 +424,7 @@ static int diffuse_coef_implicit_t(phihip_ctx* ctx, const GridView& v, const voi
     if (affine) {
         PHIHIP_TRY(ensure_buffer(ctx->ws_coef_rhs, bytes));
         CoefOp o = op;
-        coef_plan(o, 4096);
+        PHIHIP_TRY(coef_plan(o, 4096, "diffuse_implicit"));
         CoefArgs<T> a;
         memset(&a, 0, sizeof(a));
         a.a = (const T*)u; a.o1 = (T*)ctx->ws_coef_rhs.ptr; a.coef = (const T*)coef;

@@ -19,8 +19,8 @@
 // A term carries at most 1 + 3 + 2 roundings in its factors (+ 1 per wall constant cast to T, at most 2) and D in the sum: (8 + D) eps / 2 of
 // S = sum_d mean|V| (|U_hi| + |U_lo|) h_d.
 //
-// Form kept: the marching layout of diffops.hpp -- a 256-thread workgroup owns (4 rows x 64 columns) of ONE component's lattice and walks a chunk of a0
-// planes; blockIdx.y = batch entry, blockIdx.z = component, so one launch covers everything and every output sample is written once by one thread. The a0
+// Form kept: the column march of column_march.hpp (its launch plan and tile decode) over ONE component's lattice, a chunk of a0 planes per workgroup;
+// blockIdx.y = batch entry, blockIdx.z = component, so one launch covers everything and every output sample is written once by one thread. The a0
 // neighbours of U_c are carried in registers (prev / cur / next, as cgrad_kernel does); the in-plane tap offsets are loop-invariant. The velocity taps
 // of the four-face means are NOT carried: they are re-read per plane (the thread read them one plane earlier, they come from L1 / L2). No LDS, no atomics.
 //
@@ -43,7 +43,7 @@ struct MomOp {
     int bc[3][2];           // the extrapolation per internal axis / side (staggered: of u and of the velocity; centred: of u)
     double val[3][2][3];    // [axis][side][component] constants of CLOSED sides
     double h[3];            // 0.5 / dx_a
-    int tiles1, tiles2, chunk, chunks;
+    ColumnPlan plan;
 };
 
 template <typename T>
@@ -115,15 +115,9 @@ __device__ __forceinline__ T mom_mean4(const MomOp& op, const T* __restrict__ Vd
     constexpr int c = C;                                                                            \
     constexpr int lat = STAG ? C : 2;      /* the components of a centred field share one lattice */ \
     const long long b = blockIdx.y;                                                                 \
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;                                         \
-    const int bid = xcd_order(blockIdx.x, gridDim.x);                                               \
-    const int t2 = bid % op.tiles2;                                                                 \
-    const int t1 = (bid / op.tiles2) % op.tiles1;                                                   \
-    const int ch = bid / (op.tiles2 * op.tiles1);                                                   \
-    const int i1 = t1 * 4 + ty, i2 = t2 * 64 + tx;                                                  \
-    if (i1 >= op.cn[lat][1] || i2 >= op.cn[lat][2]) return;                                         \
-    const int p0 = ch * op.chunk, p1 = p0 + op.chunk < op.cn[lat][0] ? p0 + op.chunk : op.cn[lat][0]; \
-    if (p0 >= p1) return;                                                                           \
+    ColumnTile ct = column_tile(op.plan, op.cn[lat][1], op.cn[lat][2], xcd_order(blockIdx.x, gridDim.x)); \
+    if (!ct.inside || !column_planes(op.plan, ct, op.cn[lat][0])) return;                           \
+    const int i1 = ct.i1, i2 = ct.i2, p0 = ct.p0, p1 = ct.p1;                                       \
     T h[3];                                                                                         \
     _Pragma("unroll") for (int ax = 0; ax < 3; ++ax) h[ax] = (T)op.h[ax];
 
@@ -370,16 +364,7 @@ static int mom_plan(const phihip_ctx* ctx, MomOp& op, const char* what) {
         if (op.cc[c] >= (1LL << 31)) { set_error("%s: more than 2^31 samples per component and batch entry are not supported", what); return PHIHIP_ERR_UNSUPPORTED; }
         for (int a = 0; a < 3; ++a) L[a] = op.cn[c][a] > L[a] ? op.cn[c][a] : L[a];
     }
-    op.tiles1 = ceil_div(L[1], 4);
-    op.tiles2 = ceil_div(L[2], 64);
-    const long long tiles = (long long)op.tiles1 * op.tiles2;
-    int chunks = (int)((4096 + tiles - 1) / tiles);                     // ~4096 workgroups per batch entry and component when the grid allows
-    chunks = chunks > L[0] ? L[0] : (chunks < 1 ? 1 : chunks);
-    op.chunk = ceil_div(L[0], chunks);
-    if (ctx->tuning[0].chunk > 0) op.chunk = ctx->tuning[0].chunk < L[0] ? ctx->tuning[0].chunk : L[0];      // (as diff_op: an explicit setting wins)
-    op.chunks = ceil_div(L[0], op.chunk);
-    if (tiles * op.chunks >= (1LL << 31)) { set_error("%s: the grid is too large for one launch", what); return PHIHIP_ERR_UNSUPPORTED; }
-    return PHIHIP_OK;
+    return plan_columns(L, kPatchRows, kPatchCols, 4096, ctx->tuning[0].chunk, false, what, op.plan);      // ~4096 workgroups per batch entry and component; an explicit setting wins
 }
 
 static MomOp mom_op_staggered(const GridView& v) {
@@ -422,7 +407,7 @@ static MomOp mom_op_centered(const GridView& v, const ScalarBc& sb) {
 // which: 0 forward, 1 grad u, 2 grad velocity
 template <typename T, int D, bool STAG>
 static void mom_launch(const MomOp& op, int batch, int which, const MomPtrs<T>& P, hipStream_t s) {
-    const dim3 grid((unsigned)((long long)op.tiles1 * op.tiles2 * op.chunks), (unsigned)batch, (unsigned)D);
+    const dim3 grid((unsigned)((long long)op.plan.tiles1 * op.plan.tiles2 * op.plan.chunks), (unsigned)batch, (unsigned)D);
     if (which == 1) hipLaunchKernelGGL((advect_diff_grad_u_kernel<T, D, STAG>), grid, dim3(kBlock), 0, s, op, P);
     else if (which == 2) hipLaunchKernelGGL((advect_diff_grad_v_kernel<T, D, STAG>), grid, dim3(kBlock), 0, s, op, P);
     else if (STAG) hipLaunchKernelGGL((advect_diff_staggered_kernel<T, D>), grid, dim3(kBlock), 0, s, op, P);

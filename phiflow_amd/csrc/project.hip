@@ -74,7 +74,6 @@ __device__ __forceinline__ T fetch_comp(const T* C, const VelGrid& g, int ca, lo
 // divergence (phi/field/_field_math.py:617-626 with bake_extrapolation :20-39)
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr int kMaxPartialBlocks = 4096;   // patch-stride kernels: bounded number of per-block partial sums
-constexpr int kPatchCols = 64, kPatchRows = kBlock / kPatchCols;   // a workgroup visits (4 rows x 64 columns) patches of one a0 plane
 
 // uniform decode of a patch number into (plane, first row, first column): the per-thread div / mod of a linear cell index used to be
 // a third of this kernel's instructions
@@ -93,24 +92,20 @@ __device__ __forceinline__ int face_index(int i, int n, int code_lo, int code_hi
     return i;
 }
 
-// A workgroup owns a (4 rows x 64 columns) column of cells and marches over a chunk of a0 planes: the in-plane face offsets (and the
+// A column march (column_march.hpp; the scalar form decodes blockIdx.x as it is, without xcd_order): the in-plane face offsets (and the
 // boundary rule of the a1 / a2 faces) are resolved once per thread, the upper a0 face of one plane is the lower face of the next
 // (5 loads + 1 store per cell, no integer division anywhere), and the per-workgroup partial sums of div and of the active cells
 // feed fluid._balance_divergence.
 template <typename T, int DIM>
 __global__ __launch_bounds__(kBlock) void divergence_kernel(VelGrid g, CComp3<T> v, const uint8_t* flags, int flags_per_batch,
-                                                            T* __restrict__ div, double* part_sum, double* part_act, int nblk, int tiles1,
-                                                            int tiles2, int chunk, int finite_guard) {
+                                                            T* __restrict__ div, double* part_sum, double* part_act, int nblk, ColumnPlan plan,
+                                                            int finite_guard) {
     __shared__ double red[kBlock / kWave];
     const int b = blockIdx.y;
-    const int n0 = g.n[0], n1 = g.n[1], n2 = g.n[2];
-    const int tx = threadIdx.x & (kPatchCols - 1), ty = threadIdx.x / kPatchCols;
-    const int t2 = blockIdx.x % tiles2;
-    const int t1 = (blockIdx.x / tiles2) % tiles1;
-    const int c0 = blockIdx.x / (tiles2 * tiles1);
-    const int i1 = t1 * kPatchRows + ty, i2 = t2 * kPatchCols + tx;
-    const bool inside = i1 < n1 && i2 < n2;
-    const int p0 = DIM == 3 ? c0 * chunk : 0, p1 = DIM == 3 ? min(p0 + chunk, n0) : 1;
+    const int n1 = g.n[1], n2 = g.n[2];
+    ColumnTile t = column_tile(plan, n1, n2, blockIdx.x);
+    const bool active = column_planes<DIM == 3>(plan, t, g.n[0]) && t.inside;
+    const int i1 = t.i1, i2 = t.i2, p0 = t.p0, p1 = t.p1;
     const T r0 = (T)g.rdx[0], r1 = (T)g.rdx[1], r2 = (T)g.rdx[2];   // (a true division is ~10 instructions; 3 per cell made the kernel VALU-heavy)
     // in-plane taps: component 1 at rows (i1 - off1, +1), component 2 at columns (i2 - off2, +1)
     int o1[2] = {0, 0}, o2[2] = {0, 0};
@@ -136,7 +131,7 @@ __global__ __launch_bounds__(kBlock) void divergence_kernel(VelGrid g, CComp3<T>
         return C0[(long long)f * ps0 + o0];
     };
     T acc_val = T(0), acc_act = T(0);
-    if (inside && p0 < p1) {
+    if (active) {
         T lo0 = DIM == 3 ? face0(p0) : T(0);
         for (int p = p0; p < p1; ++p) {
             // explicit fma chain, the same in divergence_vec_kernel: left to the compiler's contraction the two kernels fused different pairs
@@ -182,22 +177,17 @@ __global__ __launch_bounds__(kBlock) void divergence_kernel(VelGrid g, CComp3<T>
 // `ltpr`: log2 of the threads along a row (narrow grids put more rows into a workgroup instead of idle lanes).
 template <typename T, int DIM, int V>
 __global__ __launch_bounds__(kBlock) void divergence_vec_kernel(VelGrid g, CComp3<T> v, const uint8_t* flags, int flags_per_batch,
-                                                                T* __restrict__ div, double* part_sum, double* part_act, int nblk, int tiles1,
-                                                                int tiles2, int chunk, int ltpr, int finite_guard) {
+                                                                T* __restrict__ div, double* part_sum, double* part_act, int nblk, ColumnPlan plan,
+                                                                int ltpr, int finite_guard) {
     using VT = VecA<T, V>;
     using VU = VecU<T, V>;
     using VF = Vec<uint8_t, V>;
     __shared__ double red[kBlock / kWave];
     const int b = blockIdx.y;
-    const int n0 = g.n[0], n1 = g.n[1], n2 = g.n[2];
-    const int tx = threadIdx.x & ((1 << ltpr) - 1), ty = threadIdx.x >> ltpr;
-    const int bid = xcd_order(blockIdx.x, nblk);                // neighbouring columns share an XCD's L2 (the a1 rows between them)
-    const int t2 = bid % tiles2;
-    const int t1 = (bid / tiles2) % tiles1;
-    const int c0 = bid / (tiles2 * tiles1);
-    const int i1 = t1 * (kBlock >> ltpr) + ty, i2 = ((t2 << ltpr) + tx) * V;
-    const bool inside = i1 < n1 && i2 < n2;
-    const int p0 = DIM == 3 ? c0 * chunk : 0, p1 = DIM == 3 ? min(p0 + chunk, n0) : 1;
+    const int n1 = g.n[1], n2 = g.n[2];
+    ColumnTile t = column_tile(plan, n1, n2, xcd_order(blockIdx.x, nblk), ltpr, V);      // neighbouring columns share an XCD's L2
+    const bool active = column_planes<DIM == 3>(plan, t, g.n[0]) && t.inside;
+    const int i1 = t.i1, i2 = t.i2, p0 = t.p0, p1 = t.p1;
     const T r0 = (T)g.rdx[0], r1 = (T)g.rdx[1], r2 = (T)g.rdx[2];
     const int cn2 = g.cn[2][2];
     // component 1: rows (i1 - off1, + 1); component 2: main vector at stored columns i2 .. i2 + V - 1 (faces k = 0 .. V - 1 of the V + 1 when
@@ -241,7 +231,7 @@ __global__ __launch_bounds__(kBlock) void divergence_vec_kernel(VelGrid g, CComp
         return veca_load<T, V>(C0 + (long long)f * ps0 + o0);
     };
     T acc_val = T(0), acc_act = T(0);
-    if (inside && p0 < p1) {
+    if (active) {
         VT lo0 = DIM == 3 ? face0(p0) : splat(T(0));
         for (int p = p0; p < p1; ++p) {
             VT hi0 = lo0;
@@ -378,23 +368,19 @@ static int launch_divergence(phihip_ctx* ctx, const GridView& v, const VelGrid& 
     if (vec) while (ltpr > 0 && (1 << (ltpr - 1)) * V >= v.n[2]) --ltpr;
     const int rows = vec ? kBlock >> ltpr : kPatchRows, cols = vec ? (1 << ltpr) * V : kPatchCols;
     // (rows x cols)-cell columns x chunks of planes: ~4096 workgroups per batch entry when the grid allows (2 rounds of 8 per CU)
-    const int tiles1 = ceil_div(v.n[1], rows), tiles2 = ceil_div(v.n[2], cols);
-    const long long tiles = (long long)tiles1 * tiles2;
-    PHIHIP_REQUIRE(tiles <= (1 << 24), "divergence: grid too large");
-    int chunks = v.rank == 3 ? (int)((4096 + tiles - 1) / tiles) : 1;
-    chunks = chunks > v.n[0] ? v.n[0] : (chunks < 1 ? 1 : chunks);
-    const int chunk_planes = ceil_div(v.n[0], chunks);
-    chunks = ceil_div(v.n[0], chunk_planes);
-    const int nblk = (int)tiles * chunks;
+    ColumnPlan plan;
+    PHIHIP_TRY(plan_columns(v.n, rows, cols, 4096, 0, v.rank != 3, "divergence", plan));
+    PHIHIP_REQUIRE((long long)plan.tiles1 * plan.tiles2 <= (1 << 24), "divergence: grid too large");
+    const int nblk = plan.tiles1 * plan.tiles2 * plan.chunks;
     PHIHIP_TRY(ensure_buffer(ctx->ws_div, (size_t)2 * v.batch * nblk * sizeof(double)));
     double* part_sum = (double*)ctx->ws_div.ptr;
     double* part_act = part_sum + (size_t)v.batch * nblk;
     if (vec)
         hipLaunchKernelGGL((divergence_vec_kernel<T, DIM, V>), dim3(nblk, v.batch), dim3(kBlock), 0, s, g, c, flags, fpb, (T*)div, part_sum, part_act, nblk,
-                           tiles1, tiles2, chunk_planes, ltpr, finite_guard);
+                           plan, ltpr, finite_guard);
     else
         hipLaunchKernelGGL((divergence_kernel<T, DIM>), dim3(nblk, v.batch), dim3(kBlock), 0, s, g, c, flags, fpb, (T*)div, part_sum, part_act, nblk,
-                           tiles1, tiles2, chunk_planes, finite_guard);
+                           plan, finite_guard);
     *nblk_out = nblk;
     return PHIHIP_OK;
 }
@@ -1498,7 +1484,7 @@ int run_build_cellflags(phihip_ctx* ctx, const GridView& v, const uint8_t* acces
 // ---------------------------------------------------------------------------------------------------------------------
 // diffuse.explicit, order 2: v_d += k dt * laplace(v_d) with the velocity's own padding (phi/physics/diffuse.py:13-60)
 // ---------------------------------------------------------------------------------------------------------------------
-// A workgroup owns a (4 rows x 64 columns) column of samples of one component and marches over a chunk of a0 planes (like divergence_kernel):
+// A column march over one component's lattice (column_march.hpp: launch plan and tile decode):
 // the a0 neighbours of a sample are the values the thread read one plane earlier / reads one plane ahead -- every plane is read from HBM
 // once, where the one-thread-per-sample form of rounds 1-2 pulled each plane into three different L2s (FETCH_SIZE 1.8x the array) and spent
 // a 64-bit div / mod per sample: 2-word kernel at 10 % of the HBM rate. The in-plane taps (row +-1, column +-1) and their boundary rule are
@@ -1506,21 +1492,15 @@ int run_build_cellflags(phihip_ctx* ctx, const GridView& v, const uint8_t* acces
 // ADJ: the adjoint (I + k dt L)^T as a GATHER (no atomics): the stencil is symmetric in the interior; a clamped tap returns its weight to
 // the edge sample itself, a constant tap contributes nothing, a wrapped tap is the wrapped neighbour.  gin += (...)^T gout.
 template <typename T, bool ADJ>
-__global__ __launch_bounds__(kBlock) void diffuse_kernel(VelGrid g, int ca, const T* __restrict__ vin, T* __restrict__ vout, T kdt, int tiles1, int tiles2, int chunk) {
+__global__ __launch_bounds__(kBlock) void diffuse_kernel(VelGrid g, int ca, const T* __restrict__ vin, T* __restrict__ vout, T kdt, ColumnPlan plan) {
     const int b = blockIdx.y;
     const int c0n = g.cn[ca][0], c1 = g.cn[ca][1], c2 = g.cn[ca][2];
     const long long bb = (long long)b * g.ccells[ca];
     const T* __restrict__ I = vin + bb;
     T* __restrict__ O = vout + bb;
-    const int tx = threadIdx.x & (kPatchCols - 1), ty = threadIdx.x / kPatchCols;
-    const int bid = xcd_order(blockIdx.x, gridDim.x);       // neighbouring columns share an XCD's L2 (their halo rows / columns)
-    const int t2 = bid % tiles2;
-    const int t1 = (bid / tiles2) % tiles1;
-    const int ch = bid / (tiles2 * tiles1);
-    const int i1 = t1 * kPatchRows + ty, i2 = t2 * kPatchCols + tx;
-    if (i1 >= c1 || i2 >= c2) return;
-    const int p0 = ch * chunk, p1 = min(p0 + chunk, c0n);
-    if (p0 >= p1) return;
+    ColumnTile t = column_tile(plan, c1, c2, xcd_order(blockIdx.x, gridDim.x));       // neighbouring columns share an XCD's L2 (their halo rows / columns)
+    if (!t.inside || !column_planes(plan, t, c0n)) return;
+    const int i1 = t.i1, i2 = t.i2, p0 = t.p0, p1 = t.p1;
     T w[3];
 #pragma unroll
     for (int ax = 0; ax < 3; ++ax) w[ax] = ax < g.ax0 ? T(0) : kdt / (T)(g.dx[ax] * g.dx[ax]);
@@ -1593,14 +1573,11 @@ __global__ __launch_bounds__(kBlock) void diffuse_kernel(VelGrid g, int ca, cons
 }
 
 template <typename T, bool ADJ>
-static void launch_diffuse(const VelGrid& g, int ca, int batch, const void* in, void* out, double kdt, hipStream_t s) {
-    const int tiles1 = ceil_div(g.cn[ca][1], kPatchRows), tiles2 = ceil_div(g.cn[ca][2], kPatchCols);
-    const long long tiles = (long long)tiles1 * tiles2;
-    int chunks = (int)((4096 + tiles - 1) / tiles);                     // ~4096 workgroups per batch entry when the grid allows
-    chunks = chunks > g.cn[ca][0] ? g.cn[ca][0] : (chunks < 1 ? 1 : chunks);
-    const int chunk = ceil_div(g.cn[ca][0], chunks);
-    chunks = ceil_div(g.cn[ca][0], chunk);
-    hipLaunchKernelGGL((diffuse_kernel<T, ADJ>), dim3((unsigned)(tiles * chunks), batch), dim3(kBlock), 0, s, g, ca, (const T*)in, (T*)out, (T)kdt, tiles1, tiles2, chunk);
+static int launch_diffuse(const VelGrid& g, int ca, int batch, const void* in, void* out, double kdt, hipStream_t s) {
+    ColumnPlan plan;       // ~4096 workgroups per batch entry when the grid allows
+    PHIHIP_TRY(plan_columns(g.cn[ca], kPatchRows, kPatchCols, 4096, 0, false, "diffuse", plan));
+    hipLaunchKernelGGL((diffuse_kernel<T, ADJ>), dim3((unsigned)((long long)plan.tiles1 * plan.tiles2 * plan.chunks), batch), dim3(kBlock), 0, s, g, ca, (const T*)in, (T*)out, (T)kdt, plan);
+    return PHIHIP_OK;
 }
 
 // The lattice of one staggered component (or of a centred scalar described as component `ca` of g) as a grid of the marching kernels with the
@@ -1698,7 +1675,7 @@ int run_diffuse_bwd(phihip_ctx* ctx, const GridView& v, const void* const gout[3
     LaunchScope ls(ctx, PHIHIP_K_OTHER, s);
     for (int ca = v.ax0; ca < 3; ++ca) {
         if (v.ccells[ca] >= (1LL << 31)) { set_error("diffuse: more than 2^31 samples per component and batch entry are not supported"); return PHIHIP_ERR_UNSUPPORTED; }
-        with_dtype(v, [&](auto t) { launch_diffuse<typename decltype(t)::type, true>(g, ca, v.batch, gout[ca], gin[ca], kdt, s); });
+        PHIHIP_TRY(with_dtype(v, [&](auto t) { return launch_diffuse<typename decltype(t)::type, true>(g, ca, v.batch, gout[ca], gin[ca], kdt, s); }));
     }
     PHIHIP_CHECK_HIP(hipGetLastError());
     return PHIHIP_OK;
@@ -1727,7 +1704,7 @@ int run_diffuse_centered(phihip_ctx* ctx, const GridView& v, const void* sfield,
     if (v.cells >= (1LL << 31)) { set_error("diffuse: more than 2^31 cells per batch entry are not supported"); return PHIHIP_ERR_UNSUPPORTED; }
     if (!adjoint) return diffuse_explicit_lattice(ctx, v, g, 2, sfield, out, kdt, s);
     LaunchScope ls(ctx, PHIHIP_K_OTHER, s);
-    with_dtype(v, [&](auto t) { launch_diffuse<typename decltype(t)::type, true>(g, 2, v.batch, sfield, out, kdt, s); });
+    PHIHIP_TRY(with_dtype(v, [&](auto t) { return launch_diffuse<typename decltype(t)::type, true>(g, 2, v.batch, sfield, out, kdt, s); }));
     PHIHIP_CHECK_HIP(hipGetLastError());
     return PHIHIP_OK;
 }

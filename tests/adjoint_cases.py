@@ -546,6 +546,11 @@ TILE_CASES = [
 ]
 
 
+# the diffuse adjoints march more than one plane per workgroup once tiles x planes exceeds the plan's 4096 workgroups (plan_columns, csrc/column_march.hpp):
+# one (4 x 64) tile and 4100 planes give 2 planes per workgroup, the a0 neighbours carried in registers from the first to the second. (res, bc, batch)
+CHUNKED_DIFFUSE_CASES = [((4100, 3, 5), MIX3[1], 1)]
+
+
 def _kinds(n):
     """ boundary kinds of an axis of n cells that the library stores faces for (tests/fuzz_parity.py: ONE cell between two closed sides has none) """
     return [k for k in ((PER, PER), (CLO, CLO), (OPN, OPN), (CLO, OPN), (OPN, CLO)) if not (n == 1 and k == (CLO, CLO))]

@@ -20,7 +20,7 @@ one number's rounding error has a sign and can cancel, so the yardstick is the V
 to first order, with |delta r|_2 / |r|_2 <= 4 e_r32 + 16 eps; the same for sum y^2 with the right-hand-side vector (the kernel accumulates y^2 in the element
 type). Every check prints its figures (lines starting with "DCEW") before it asserts.
 
-Each case asserts the launch plan it is there for (`plan` restates coef_plan; PLANS holds the expected figures as literals): a later change to the plan makes the
+Each case asserts the launch plan it is there for (`plan` restates plan_columns of csrc/column_march.hpp as coef_plan calls it; PLANS holds the expected figures as literals): a later change to the plan makes the
 case complain, not silently stop covering.
 """
 import functools
@@ -49,7 +49,7 @@ PAIRS = [(p % 5, 'PZK0'[p % 4]) for p in range(20)]                             
 
 
 def plan(res, target):
-    """ coef_plan's arithmetic: (4 x 64)-cell tiles in the plane, a0 split into chunks so that a batch entry has about `target` workgroups.
+    """ plan_columns (csrc/column_march.hpp) as coef_plan calls it: (4 x 64)-cell tiles in the plane, a0 split into chunks so that a batch entry has about `target` workgroups.
     Returns (tiles1, tiles2, chunk, chunks, planes in the last chunk) """
     n = (1,) * (3 - len(res)) + tuple(res)
     tiles1, tiles2 = (n[1] + 3) // 4, (n[2] + 63) // 64

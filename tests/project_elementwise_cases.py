@@ -61,7 +61,7 @@ def vec_cells(dtype):
 
 
 def divergence_plan(res, dtype, aligned=True):
-    """ project.hip:373-396 divergence_vec_ok / launch_divergence """
+    """ project.hip divergence_vec_ok / launch_divergence: the tile shape, then plan_columns (csrc/column_march.hpp) with target 4096, one chunk on 2-D grids """
     n0, n1, n2 = ([1] * (3 - len(res)) + list(res))
     V = vec_cells(dtype)
     vec = aligned and n2 % V == 0

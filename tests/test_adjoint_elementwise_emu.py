@@ -42,6 +42,14 @@ def test_every_entry_point_on_axes_of_one_to_three_cells(emu_ctx, case, dtype):
 
 
 @DTYPES
+@pytest.mark.parametrize("case", A.CHUNKED_DIFFUSE_CASES, ids=_id)
+def test_diffuse_adjoints_march_several_planes(emu_ctx, case, dtype):
+    """ a thin grid of many planes: every workgroup of the diffuse adjoints carries its a0 neighbours over a chunk of two planes """
+    res, bc, batch = case
+    A.run_case(emu_ctx, MEM, res, bc, dtype, batch, seed=3, entries=('diffuse',))
+
+
+@DTYPES
 @pytest.mark.parametrize("shared", [False, True], ids=["per-batch", "shared"])
 @pytest.mark.parametrize("case", A.GRID_SAMPLE_CASES, ids=_id)
 def test_grid_sample_backward(emu_ctx, case, shared, dtype):

@@ -51,6 +51,14 @@ def test_every_entry_point_on_large_grids(ctx, mem, case, dtype):
     A.run_case(ctx, mem, res, bc, dtype, batch, dt, seed=4, k0=k0, slab_axis=slab_axis)
 
 
+@DTYPES
+@pytest.mark.parametrize("case", A.CHUNKED_DIFFUSE_CASES, ids=_id)
+def test_diffuse_adjoints_march_several_planes(ctx, mem, case, dtype):
+    """ a thin grid of many planes: every workgroup of the diffuse adjoints carries its a0 neighbours over a chunk of two planes """
+    res, bc, batch = case
+    A.run_case(ctx, mem, res, bc, dtype, batch, seed=3, entries=('diffuse',))
+
+
 def test_extruded_256_cubed_fp32_reaches_the_block_cap(ctx, mem):
     """ 256^3 periodic staggered advection of an extruded 2-D flow: every plane of the field gradient and of the in-plane velocity gradients against the 2-D
     reference of that plane """
